@@ -15,9 +15,15 @@ keeps 256^3 for every N. torch.distributed only carries the rendezvous (RCCL uni
 the max-over-ranks reduction of the step time.
 
 The JSON line carries `roofline` (dominant kernel = the Jacobi sweep: 12 algorithmic bytes per cell-sweep,
-timed with HIP events on the kernel's own stream inside the timed region) and `cpu_baseline` (the CPU
-oracle -- a scalar C++ port of the reference shaders, OpenMP over planes -- timed on the host cores on a
-bounded sample of the same workload).  The oracle is used ONLY for that reported baseline.
+timed with HIP events on the kernel's own stream inside the timed region).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the bench measures
+behind the timed steps: `cpu_baseline` (the CPU oracle -- a scalar C++ port of the reference shaders, OpenMP over
+planes -- timed on the host cores on a bounded sample of the same workload; the oracle is used ONLY for that reported
+baseline), `warm_device`, the `render` leg, `developed_plume` and, for N > 1, `peer_transport`.
+
+--dump-outputs DIR writes the fields the last timed step left (velocity, colour, pressure) as float32 .npy files
+(dump_outputs below), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -232,6 +238,35 @@ def cpu_baseline(grid, iters, budget_s=20.0, mode=0, half=False, address=0):
             "sample": fmt % (steps, iters, grid, grid, nz, grid, threads, sorted(tried), ncores) + "; value = median of %d timings" % len(rates)}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much in all
+DUMP_SAMPLE_CELLS = 1 << 20        # cells kept per field when the whole fields exceed the budget (3 + 4 + 1 floats each: 34 MB)
+DUMP_SEED = 1234
+
+
+def dump_outputs(fluid, out_dir):
+    """--dump-outputs: what a caller of UpdateFrame + Simulate reads back after the last timed step -- velocity (3, Z, Y, X), colour
+    (Z, Y, X, 4) and pressure (Z, Y, X) -- as float32 <out_dir>/{velocity,color,pressure}.npy.  Fields that fit DUMP_BUDGET_BYTES are
+    written whole; larger ones as the same DUMP_SAMPLE_CELLS cells of every field (flat (z, y, x) indices drawn with DUMP_SEED, in
+    increasing order): velocity (n, 3), colour (n, 4), pressure (n,).  The sample depends on the grid alone, so two builds run with the
+    same arguments write comparable files.  One field is on the host at a time (fx_download takes whole fields): the colour's 16 B per
+    cell is the peak, 2.1 GB at 512^3, 17 GB at 1024^3."""
+    import numpy as np
+    from fluidx12_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    for name, field, comps in (("pressure", capi.FIELD_PRESSURE, 1), ("velocity", capi.FIELD_VELOCITY, 3), ("color", capi.FIELD_COLOR, 4)):
+        a = fluid.download(field)
+        if name == "pressure":
+            cells = a.size
+            if cells * (1 + 3 + 4) * 4 > DUMP_BUDGET_BYTES:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cells, min(cells, DUMP_SAMPLE_CELLS), replace=False))
+        if idx is not None:
+            a = a.reshape(3, cells)[:, idx].T if name == "velocity" else a.reshape(cells, comps)[idx] if comps > 1 else a.reshape(cells)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        del a
+    return ["color", "pressure", "velocity"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -284,7 +319,18 @@ def main():
                          "RCCL refuses two ranks on one device); never a measurement, the JSON line says so")
     ap.add_argument("--dry-run", action="store_true",
                     help="distributed plumbing only (no GPU work); used by the gloo CPU tests, never a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure: the CPU baseline, the `warm_device` leg, the render leg, the "
+                         "developed plume and (N > 1) the peer-transport leg; the --no-* switches above pick among them.  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single domain: write the velocity, colour and pressure fields the last timed step left as float32 DIR/<name>.npy "
+                         "(a fixed, seeded sample of cells when the fields exceed 64 MB)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_render = args.no_developed = args.no_warm_leg = args.no_peer_leg = True
+    if args.dump_outputs and (args.gpus > 1 or args.loopback > 1 or args.dry_run):
+        ap.error("--dump-outputs needs a single-domain run (--gpus 1, no --loopback, no --dry-run)")
     # (the CPU baseline's OpenMP threads are left to the scheduler: pinned with OMP_PROC_BIND=close / OMP_PLACES=cores the same sample ran at
     # 15.8 instead of 56 M voxel-updates/s on the box of round 6 -- the visible CPUs of a container are not its cores; unpinned the three
     # timings of a run agree to 3 %)
@@ -572,6 +618,9 @@ def main():
 
     elapsed = max_over_ranks(elapsed)
     watch.disarm()
+    if args.dump_outputs:
+        names = dump_outputs(fluid, args.dump_outputs)
+        sys.stderr.write("bench.py: wrote %s under %s\n" % (", ".join(n + ".npy" for n in names), args.dump_outputs))
 
     # ---- N > 1: certify what was timed.  Every rank takes a device-side digest of its OWNED planes of velocity, colour and pressure
     # (fx_field_digest: a sum over the elements of a mix of (stored bits, global position) -- independent of the decomposition); rank 0

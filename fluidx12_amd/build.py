@@ -106,6 +106,17 @@ def build_lib(force=False, verbose=False):
     return LIB
 
 
+def lab_sources():
+    """the sources -DFX_LAB changes (they test `FX_LAB`); all of them if a header does.  A lab build recompiles these and links every other
+    object of the regular build (__graft_entry__.build -> tools/_variants/libfluidx_hip_lab.so)"""
+    import re
+    pat = re.compile(r"\bFX_LAB\b")
+    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
+    if any(pat.search(open(h).read()) for h in hdrs):
+        return tuple(SOURCES)
+    return tuple(s for s in SOURCES if pat.search(open(os.path.join(CSRC, s)).read()))
+
+
 def build_variant(name, defs, sources=("fx_jacobi_strip4.hip",), outdir=None):
     """A lab build of the library: `sources` recompiled with the extra `defs` (e.g. ["-DFX_S4_NOHAND"]: leave-one-out timing builds of the
     four-sweep kernels, docs/LAB.md), every other object taken from the regular build; -> <outdir>/libfluidx_hip_<name>.so.  The tools

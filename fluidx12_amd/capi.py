@@ -119,7 +119,7 @@ def load():
     except Exception:  # torch is plumbing, not a requirement
         pass
     path = _build.ensure_built()
-    if os.environ.get("FLUIDX_LIB_PATH"):          # a lab build of the library (build.build_variant): tools only -- tests and bench.py never set it
+    if os.environ.get("FLUIDX_LIB_PATH"):          # a lab build of the library (build.build_variant): tools, and tests/conftest.py `knob` while a test runs on the lab build; bench.py never sets it
         path = os.environ["FLUIDX_LIB_PATH"]
     if not os.path.exists(path):
         raise RuntimeError("libfluidx_hip.so is missing and could not be built")

@@ -67,3 +67,41 @@ def test_committed_summaries_of_the_headline_kernels_are_fresh():
     for kernel, grid, iters, storage in (("k_jacobi_strip4o", 256, 40, "fp32"), ("k_jacobi_block2", 128, 40, "fp32"), ("k_jacobi_strip4x", 512, 80, "fp32"), ("k_jacobi_strip4t", 384, 40, "fp32")):
         t = b.pmc_traffic(kernel, grid, iters, storage)
         assert t is not None and t[2] is False, (kernel, t)
+
+
+def test_dump_outputs_samples_large_fields_the_same_way_every_time(tmp_path):
+    """--dump-outputs (bench.dump_outputs): fields over the 64 MB budget are written as one seeded sample of cells, the same cells of every
+    field; small fields whole.  Here on host arrays standing in for a context's downloads."""
+    import numpy as np
+    from fluidx12_amd import capi
+    b = load_bench()
+
+    class FakeFluid:
+        def __init__(self, shape):
+            Z, Y, X = shape
+            n = Z * Y * X
+            c = np.arange(n, dtype=np.float32)
+            self.fields = {capi.FIELD_VELOCITY: np.stack([c, c + 0.25, c + 0.5]).reshape(3, Z, Y, X),
+                           capi.FIELD_COLOR: np.stack([c, c + 1, c + 2, c + 3], axis=-1).reshape(Z, Y, X, 4), capi.FIELD_PRESSURE: c.reshape(Z, Y, X)}
+
+        def download(self, field):
+            return self.fields[field].copy()
+
+    small = FakeFluid((8, 16, 16))
+    assert b.dump_outputs(small, str(tmp_path / "small")) == ["color", "pressure", "velocity"]
+    for field, name in ((capi.FIELD_VELOCITY, "velocity"), (capi.FIELD_COLOR, "color"), (capi.FIELD_PRESSURE, "pressure")):
+        assert np.array_equal(np.load(tmp_path / "small" / (name + ".npy")), small.fields[field])
+
+    big = FakeFluid((128, 128, 128))                       # 8 floats per cell x 2 M cells = 67 MB: sampled
+    for run in ("a", "b"):
+        b.dump_outputs(big, str(tmp_path / run))
+    total = 0
+    for name in ("velocity", "color", "pressure"):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float32 and len(x) == b.DUMP_SAMPLE_CELLS and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= b.DUMP_BUDGET_BYTES
+    cells = np.load(tmp_path / "a" / "pressure.npy")         # the stand-in's pressure is the flat cell index
+    assert (np.diff(cells) > 0).all() and cells[-1] < 128 ** 3
+    assert np.array_equal(np.load(tmp_path / "a" / "velocity.npy"), np.stack([cells, cells + 0.25, cells + 0.5], axis=1))
+    assert np.array_equal(np.load(tmp_path / "a" / "color.npy"), np.stack([cells, cells + 1, cells + 2, cells + 3], axis=1))

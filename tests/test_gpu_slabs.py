@@ -694,7 +694,8 @@ def test_bench_single_gpu_line_is_complete():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--grid", "128", "--steps", "20", "--warmup", "5", "--cpu-budget", "2"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--grid", "128", "--steps", "20", "--warmup", "5", "--cpu-budget", "2",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -736,7 +737,7 @@ def test_bench_reference_configuration_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reference-config", "--grid", "128", "--steps", "20", "--warmup", "12",
-                          "--cpu-budget", "2", "--no-render"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--cpu-budget", "2", "--no-render", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["config"]["jacobi_mode"] == "faithful" and d["config"]["jacobi_iters"] == 64 and d["config"]["storage"] == "fp16"
@@ -1007,7 +1008,7 @@ def test_peer_group_across_two_devices():
     Needs a second GPU (the driver's boxes have one: skipped there)."""
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("one device")
+        pytest.skip("needs 2 GPUs, found %d" % torch.cuda.device_count())
     dims, steps = (64, 64, 64), 6
     ref = run_single(dims, steps, jacobi_iters=20)
     fl = []

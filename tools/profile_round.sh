@@ -37,7 +37,7 @@ prof reference "--grid 256 --iters 64 --storage fp16 --mode faithful --steps-pro
 fi
 render() {  # tag, summary args, bench args...
   tag=$1; sargs=$2; shift 2
-  B="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-developed --no-warm-leg $*"
+  B="python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-developed --no-warm-leg $*"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/rkt_$tag -o k -- $B > /dev/null 2>&1
   rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/rl2_$tag -o p -- $B > /dev/null 2>&1
   rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --output-format csv -d $O/rl1_$tag -o p -- $B > /dev/null 2>&1
@@ -52,17 +52,17 @@ render config5 "--grid 256 --storage fp16 --has-sh" --config 5
 mkdir -p profiles
 if [ -n "$ONLY_RENDER" ]; then cp $O/render_pmc_*.json profiles/ 2>/dev/null; for f in $O/render_pmc_*.json; do cp $f profiles/${TAG}_$(basename $f); done; exit 0; fi
 for f in $O/pmc_traffic_*.json $O/sq_counters_*.json $O/render_pmc_*.json; do cp $f profiles/${TAG}_$(basename $f); done
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20_warmup5.json 2>> $O/bench.err
-python bench.py --config 2 --steps 100 --warmup 16 --no-cpu-baseline > $O/bench_128.json 2>> $O/bench.err
-python bench.py --config 4 --steps 10 --warmup 3 --no-cpu-baseline --no-render > $O/bench_512_80.json 2>> $O/bench.err
-python bench.py --config 5 --no-cpu-baseline > $O/bench_fp16.json 2>> $O/bench.err
-python bench.py --grid 150 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_150.json 2>> $O/bench.err
-python bench.py --grid 384 --steps 30 --warmup 10 --no-cpu-baseline --no-render > $O/bench_384.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20_warmup5.json 2>> $O/bench.err
+python bench.py --full --config 2 --steps 100 --warmup 16 --no-cpu-baseline > $O/bench_128.json 2>> $O/bench.err
+python bench.py --full --config 4 --steps 10 --warmup 3 --no-cpu-baseline --no-render > $O/bench_512_80.json 2>> $O/bench.err
+python bench.py --full --config 5 --no-cpu-baseline > $O/bench_fp16.json 2>> $O/bench.err
+python bench.py --full --grid 150 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_150.json 2>> $O/bench.err
+python bench.py --full --grid 384 --steps 30 --warmup 10 --no-cpu-baseline --no-render > $O/bench_384.json 2>> $O/bench.err
 python bench.py --grid 1024 --steps 4 --warmup 2 --no-cpu-baseline --no-render --no-developed --no-warm-leg > $O/bench_1024.json 2>> $O/bench.err
-python bench.py --reference-config > $O/bench_reference.json 2>> $O/bench.err
-python bench.py --reference-config --grid 128 --no-cpu-baseline > $O/bench_reference_128.json 2>> $O/bench.err
-python bench.py --reference-config --grid 150 --no-cpu-baseline > $O/bench_reference_150.json 2>> $O/bench.err
+python bench.py --full --reference-config > $O/bench_reference.json 2>> $O/bench.err
+python bench.py --full --reference-config --grid 128 --no-cpu-baseline > $O/bench_reference_128.json 2>> $O/bench.err
+python bench.py --full --reference-config --grid 150 --no-cpu-baseline > $O/bench_reference_150.json 2>> $O/bench.err
 for g in shared peer; do
   for n in 2 4; do python bench.py --loopback $n --group $g --steps 25 --warmup 5 --no-cpu-baseline --no-render --no-developed > $O/bench_loopback${n}_$g.json 2>> $O/bench.err; done
   python bench.py --config 4 --loopback 8 --group $g --steps 6 --warmup 2 --no-cpu-baseline --no-render --no-developed > $O/bench_loopback8_config4_$g.json 2>> $O/bench.err

@@ -2,7 +2,7 @@
 """Summarise the render kernels of a profiled bench.py run: average duration (rocprofv3 --kernel-trace --stats) and cache hit rates
 (two --pmc passes) at the frame bench.py pins its render leg to (132).
 
-    B="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline [--config 5]"
+    B="python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline [--config 5]"
     rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- $B
     rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/l2 -o p -- $B
     rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --output-format csv -d $O/l1 -o p -- $B
