@@ -20,7 +20,8 @@ FLAG_JACOBI_FUSE_MASK, FLAG_NO_OVERLAP, FLAG_RENDER_ONLY = 0xF, 0x10, 0x20
 OPT_OVERLAP, OPT_JACOBI_ROUND, OPT_ADAPTIVE_HALO, OPT_COUNT_SAMPLES, OPT_RENDER_ACCEL = 1, 2, 3, 4, 5
 ABI_VERSION = 7                      # FX_ABI_VERSION of include/fluidx_hip.h
 (FIELD_VELOCITY, FIELD_VELOCITY1, FIELD_COLOR, FIELD_COLOR_PREV, FIELD_PRESSURE, FIELD_DIVERGENCE,
- FIELD_LIGHTMAP, FIELD_CUBEMAP, FIELD_TARGET, FIELD_TARGET_FLOAT) = range(10)
+ FIELD_LIGHTMAP, FIELD_CUBEMAP, FIELD_TARGET, FIELD_TARGET_FLOAT, FIELD_CUBE_DEPTH) = range(11)
+DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is device memory, read in place
 
 
 class Desc(C.Structure):
@@ -79,6 +80,7 @@ SYMBOLS = {
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),
     "fx_clear_render_target": (C.c_int, [_vp, _vp, _fp]),
     "fx_render_cube": (C.c_int, [_vp, _vp, C.c_uint8]),
+    "fx_set_scene_depth": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32]),
     "fx_dds_cube_info": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fx_dds_decode_cube": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _fp, C.c_size_t]),
     "fx_timing_enable": (C.c_int, [_vp, C.c_int]),

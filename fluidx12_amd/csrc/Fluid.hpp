@@ -53,6 +53,7 @@ public:
 		d.storage = opt.storage; d.jacobi_iters = opt.jacobiIters; d.jacobi_mode = opt.jacobiMode;
 		d.advect_address = opt.advectAddress; d.device = opt.device;
 		m_status = fx_create(&m_ctx, &d);
+		m_width = width; m_height = height;
 		return m_status == FX_OK;
 	}
 	void SetMaxSamples(uint32_t maxRaySamples, uint32_t maxLightSamples) { m_status = fx_set_max_samples(m_ctx, maxRaySamples, maxLightSamples); }
@@ -76,7 +77,15 @@ public:
 		m_status = fx_clear_render_target(m_ctx, pCommandList, clearColor);
 		m_hasTarget = m_status == FX_OK;
 	}
-	void UseRenderTarget() { m_hasTarget = true; }       // something (the sky pass) has drawn on the target: Render resolves onto it
+	void UseRenderTarget() { m_hasTarget = true; }
+	// the scene's depth buffer for the following renders (the reference's _HAS_DEPTH_MAP_ variants; fx_set_scene_depth): float[height][width]
+	// of the Init viewport, 0 = near, 1 = far plane, under UpdateFrame's projection with planes zNear / zFar.  onDevice: `depth` is device
+	// memory read in place by every later Render (keep it alive); otherwise it is copied.  nullptr detaches.
+	bool SetSceneDepth(const float* depth, float zNear, float zFar, bool onDevice = false)
+	{
+		m_status = fx_set_scene_depth(m_ctx, nullptr, depth, m_width, m_height, zNear, zFar, onDevice ? FX_DEPTH_DEVICE : 0u);
+		return m_status == FX_OK;
+	}       // something (the sky pass) has drawn on the target: Render resolves onto it
 	// read the RGBA8 target back (the reference's screen-shot path reads the back buffer, FluidX12.cpp:640-660)
 	bool ReadRenderTarget(std::vector<uint8_t>& rgba)
 	{
@@ -101,6 +110,7 @@ protected:
 	fx_ctx* m_ctx;
 	int m_status = FX_OK;
 	bool m_hasTarget = false;
+	uint32_t m_width = 0, m_height = 0;
 };
 
 // SH side of class LightProbe (LightProbe.h:16-26); the DDS loader and the sky pass are out of scope

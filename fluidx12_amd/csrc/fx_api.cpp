@@ -58,7 +58,7 @@ int fx_update_frame(fx_ctx* ctx, float time_step, uint8_t frame_index,
 				for (int q = 0; q < 4; ++q) c->fc.s2w[r * 4 + q] = vpI.m[q][r];
 			const Mat4 wvpI = wvp.inverse();                                    // stored transposed (Fluid.cpp:318)
 			for (int r = 0; r < 4; ++r)
-				for (int q = 0; q < 4; ++q) c->fc.wvp_i[r * 4 + q] = wvpI.m[q][r];
+				for (int q = 0; q < 4; ++q) { c->fc.wvp_i[r * 4 + q] = wvpI.m[q][r]; c->wvp[r * 4 + q] = wvp.m[q][r]; }   // (the forward one: scene depth)
 			for (int a = 0; a < 3; ++a) c->fc.eye_pt[a] = eye[a];
 			const float pi = 3.141592654f;
 			const float lp[3] = { 75.0f, 75.0f, -75.0f };                        // Fluid.cpp:169-173
@@ -130,12 +130,28 @@ static int ensure_target(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// the scene depth's kernel argument (fx_set_scene_depth) for the cube mip `lod` (fx_render, fx_render_cube); false when none is attached
+static bool depth_args(const fx_ctx* c, uint32_t lod, DepthArgs* da)
+{
+	if (!c->depth) return false;
+	da->depth = c->depth;
+	da->W = (int)c->desc.viewport_w; da->H = (int)c->desc.viewport_h;
+	std::memcpy(da->wvp, c->wvp, sizeof da->wvp);
+	da->z_near = c->depth_zn; da->z_far = c->depth_zf;
+	da->cube_depth = reinterpret_cast<float*>(reinterpret_cast<char*>(c->cube_depth) + c->cube_mip_offset[lod]);
+	return true;
+}
+
 // The marches of one fx_render.  FX_OPT_RENDER_ACCEL (default): the acceleration structures of this frame's colour field are built
 // first, inside the first pass's timing mark -- their cost belongs to the frame.
 struct Marches {
 	fx_ctx* c; const void* color; hipStream_t s; unsigned long long* cnt; bool accel, built, filled;
+	DepthArgs da; const DepthArgs* dep;             // the scene depth of the view marches (null: none attached)
 	Marches(fx_ctx* ctx, const void* col, hipStream_t st, unsigned long long* counters)
-		: c(ctx), color(col), s(st), cnt(counters), accel(ctx->opt_render_accel && ctx->accel_ok), built(false), filled(false) {}
+		: c(ctx), color(col), s(st), cnt(counters), accel(ctx->opt_render_accel && ctx->accel_ok), built(false), filled(false)
+	{
+		dep = depth_args(ctx, ctx->cube_lod, &da) ? &da : nullptr;
+	}
 	const float* sh() const { return c->has_sh ? c->sh_dev : nullptr; }
 	hipError_t build(bool for_light = false)
 	{
@@ -176,9 +192,9 @@ struct Marches {
 		if (e != hipSuccess) return e;
 		const uint32_t ns = c->ray_samples;
 		if (accel) return launch_accel_view(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), size,
-			c->visibility_mask, ns, c->max_light_samples, separate, cube, c->accel, s, cnt);
+			c->visibility_mask, ns, c->max_light_samples, separate, cube, c->accel, s, cnt, dep);
 		return launch_raymarch_view(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), size,
-			c->visibility_mask, ns, c->max_light_samples, separate, cube, s, cnt);
+			c->visibility_mask, ns, c->max_light_samples, separate, cube, s, cnt, dep);
 	}
 	hipError_t direct(int W, int H, bool separate)      // rayCastVDirect Fluid.cpp:953-972 / rayCastDirect :932-951
 	{
@@ -186,9 +202,9 @@ struct Marches {
 		if (e != hipSuccess) return e;
 		const uint32_t ns = separate ? c->ray_samples : c->max_ray_samples;
 		if (accel) return launch_accel_direct(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), W, H,
-			ns, c->max_light_samples, separate, c->target, c->target_float, c->accel, s, cnt);
+			ns, c->max_light_samples, separate, c->target, c->target_float, c->accel, s, cnt, dep);
 		return launch_raycast_direct(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), W, H,
-			ns, c->max_light_samples, separate, c->target, c->target_float, s, cnt);
+			ns, c->max_light_samples, separate, c->target, c->target_float, s, cnt, dep);
 	}
 };
 
@@ -241,6 +257,7 @@ int fx_render(fx_ctx* ctx, void* stream, uint8_t frame_index, uint8_t flags)
 		ScopedMark mk(ctx, s, MK_VIEW);
 		FX_HIP(m.view(size, cube, separate));
 	}
+	ctx->cube_depth_on[ctx->cube_lod] = m.dep != nullptr;          // what fx_render_cube resolves this mip with
 	if (ctx->timing_on) ctx->acc.renders += 1;
 	return FX_OK;
 }
@@ -265,9 +282,40 @@ int fx_render_cube(fx_ctx* ctx, void* stream, uint8_t frame_index)
 	hipStream_t s = pick_stream(ctx, stream);
 	int rc = ensure_target(ctx, s);
 	if (rc) return rc;
+	// the depth-aware CubeCast only for a cube map that was marched with depth, and while depth is attached
+	DepthArgs da;
+	const bool dep = ctx->cube_depth_on[ctx->cube_lod] && depth_args(ctx, ctx->cube_lod, &da);
 	ScopedMark mk(ctx, s, MK_RESOLVE);
 	FX_HIP(launch_resolve_cube(ctx->cube + ctx->cube_mip_offset[ctx->cube_lod], ctx->g.X >> ctx->cube_lod, ctx->fc,
-		(int)ctx->desc.viewport_w, (int)ctx->desc.viewport_h, ctx->target, ctx->target_float, s));
+		(int)ctx->desc.viewport_w, (int)ctx->desc.viewport_h, ctx->target, ctx->target_float, s, dep ? &da : nullptr));
+	return FX_OK;
+}
+
+int fx_set_scene_depth(fx_ctx* ctx, void* stream, const float* depth, uint32_t width, uint32_t height, float z_near, float z_far, uint32_t flags)
+{
+	if (!ctx || (flags & ~FX_DEPTH_DEVICE)) return FX_E_INVALID;
+	// 2-D grids have no depth variant (PSVisualizeColor); a context without a viewport or a slab of a group does not march view rays
+	if (ctx->g.Zg <= 1 || !ctx->cube_depth || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	if (!depth) { ctx->depth = nullptr; return FX_OK; }
+	if (width != ctx->desc.viewport_w || height != ctx->desc.viewport_h || !(0.0f < z_near && z_near < z_far)) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	if (flags & FX_DEPTH_DEVICE) {
+		// read in place by the kernels: it must be memory this device can address (a host pointer here would fault the first render)
+		hipPointerAttribute_t at;
+		if (hipPointerGetAttributes(&at, depth) != hipSuccess) { (void)hipGetLastError(); return FX_E_INVALID; }
+		if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) return FX_E_INVALID;
+		if (at.type == hipMemoryTypeDevice && at.device != ctx->device) return FX_E_INVALID;
+		ctx->depth = depth;
+	} else {
+		const size_t bytes = (size_t)width * height * sizeof(float);
+		if (!ctx->depth_own) FX_HIP(hipMalloc((void**)&ctx->depth_own, bytes));
+		hipStream_t s = pick_stream(ctx, stream);
+		FX_HIP(hipMemcpyAsync(ctx->depth_own, depth, bytes, hipMemcpyHostToDevice, s));   // behind the renders that read the previous copy
+		FX_HIP(hipStreamSynchronize(s));                                                    // the caller's buffer may go when this returns
+		ctx->depth = ctx->depth_own;
+	}
+	ctx->depth_zn = z_near;
+	ctx->depth_zf = z_far;
 	return FX_OK;
 }
 

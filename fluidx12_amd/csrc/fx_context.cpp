@@ -84,7 +84,7 @@ void free_all(fx_ctx* c)
 		if (c->col[i]) (void)hipFree(c->col[i]);
 		if (c->p[i]) (void)hipFree(c->p[i]);
 	}
-	void* others[] = { c->env, c->accel.occ, c->accel.alpha, c->accel.bits, c->accel.list, c->accel.cells, c->accel.gi, c->accel.ctr, c->target, c->target_float, c->p_face[0], c->p_face[1], c->b, c->frozen, c->frozen_alt, c->lightmap, c->cube, c->sh_dev, c->halo_overflow, c->stage,
+	void* others[] = { c->env, c->cube_depth, c->depth_own, c->accel.occ, c->accel.alpha, c->accel.bits, c->accel.list, c->accel.cells, c->accel.gi, c->accel.ctr, c->target, c->target_float, c->p_face[0], c->p_face[1], c->b, c->frozen, c->frozen_alt, c->lightmap, c->cube, c->sh_dev, c->halo_overflow, c->stage,
 		c->sh_scratch[0], c->sh_scratch[1], c->sh_scratch[2], c->sh_scratch[3], c->p_aux, c->fz_mask[0], c->fz_mask[1], c->fz_mask[2], c->fz_tile_next, c->fz_stat, c->fz_list[0], c->fz_list[1], c->fz_counts, c->sample_counters, c->adv_far };
 	for (void* q : others) if (q) (void)hipFree(q);
 	for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -236,6 +236,10 @@ int fx_create(fx_ctx** out, const fx_desc* d)
 			}
 			FX_HIP(hipMalloc((void**)&ctx->cube, off));
 			FX_HIP(hipMemsetAsync(ctx->cube, 0, off, ctx->stream));
+			if (d->viewport_w && d->viewport_h) {                            // the scene depth's cube (Fluid.cpp:234-236): far plane everywhere
+				FX_HIP(hipMalloc((void**)&ctx->cube_depth, off));
+				FX_HIP(hipMemsetD32Async((hipDeviceptr_t)ctx->cube_depth, 0x3f800000, off / 4, ctx->stream));
+			}
 			// rays cross slabs: only whole grids render.  The accelerated marches address their volumes by 32-bit byte offsets (16-byte texels:
 			// 2^28 voxels, 645^3); larger grids keep the plain kernels
 			if (!slab && ctx->g.cells_owned() <= ((size_t)1 << 28) && ctx->g.X >= 4) {        // (rows of >= 2 voxels: the x taps travel in pairs)
@@ -368,6 +372,12 @@ static int field_info(fx_ctx* c, int field, size_t* host_bytes)
 		*host_bytes = 6 * s * s * 4;
 		return FX_OK;
 	}
+	case FX_FIELD_CUBE_DEPTH: {
+		if (!c->cube_depth) return FX_E_INVALID;
+		const size_t s = (size_t)c->g.X >> c->cube_lod;
+		*host_bytes = 6 * s * s * 4;
+		return FX_OK;
+	}
 	case FX_FIELD_TARGET: case FX_FIELD_TARGET_FLOAT:
 		if (!c->target) return FX_E_STATE;
 		*host_bytes = (size_t)c->desc.viewport_w * c->desc.viewport_h * (field == FX_FIELD_TARGET ? 4 : 16);
@@ -477,6 +487,7 @@ int fx_upload(fx_ctx* ctx, int field, const void* host, size_t bytes)
 		break;
 	case FX_FIELD_CUBEMAP:       // mip `cube_lod`: lets the resolve be driven with a known cube map (parity tests, replays)
 		FX_HIP(hipMemcpy(ctx->cube + ctx->cube_mip_offset[ctx->cube_lod], host, need, hipMemcpyHostToDevice));
+		ctx->cube_depth_on[ctx->cube_lod] = false;    // not a march with depth: the resolve of this cube map weights no tap
 		break;
 	default:
 		return FX_E_INVALID;     // light map / render target are outputs
@@ -529,6 +540,9 @@ int fx_download(fx_ctx* ctx, int field, void* host, size_t bytes)
 		break;
 	case FX_FIELD_CUBEMAP:
 		FX_HIP(hipMemcpy(host, ctx->cube + ctx->cube_mip_offset[ctx->cube_lod], need, hipMemcpyDeviceToHost));
+		break;
+	case FX_FIELD_CUBE_DEPTH:
+		FX_HIP(hipMemcpy(host, (const char*)ctx->cube_depth + ctx->cube_mip_offset[ctx->cube_lod], need, hipMemcpyDeviceToHost));
 		break;
 	case FX_FIELD_TARGET:
 		FX_HIP(hipMemcpy(host, ctx->target, need, hipMemcpyDeviceToHost));

@@ -52,6 +52,13 @@ struct fx_ctx {
 	uint32_t* lightmap;             // R11G11B10F packed (m_lightMap), owned planes only
 	uint8_t* cube;                  // RGBA8 cube map, 5 mips back to back (m_cubeMap)
 	size_t cube_mip_offset[5];
+	float* cube_depth;              // float cube depth beside the cube map, every mip at the cube's byte offsets (4 bytes a texel), initialised to 1.0
+	bool cube_depth_on[5];          // the mip was last marched with a scene depth attached (fx_render_cube then weights its taps by depth)
+	// scene depth (fx_set_scene_depth; render state: kept across fx_update_frame, never checkpointed)
+	const float* depth;             // float[viewport_h][viewport_w] the depth variants read: the caller's device buffer or depth_own; null = detached
+	float* depth_own;               // the context's copy of a host depth buffer (lazily allocated)
+	float depth_zn, depth_zf;
+	float wvp[16];                  // CBPerObject.WorldViewProj (Fluid.cpp:315-318) as its four constant-buffer rows, set by fx_update_frame
 	float* env;                     // radiance cube of the sky pass, float [6][env_n][env_n][3] (fx_set_environment)
 	uint32_t env_n;
 	fx::RenderAccel accel = {};     // scratch of the accelerated ray marches (occupancy grid + masks, alpha side volume, light-voxel list), rebuilt per fx_render

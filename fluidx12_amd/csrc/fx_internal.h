@@ -38,6 +38,16 @@ struct FrameConsts {
 	float s2w[16];         // LightProbe's ScreenToWorld = transpose(inverse(view * proj)) rows (LightProbe.cpp:70-76)
 };
 
+// scene depth of the view-ray kernels (the reference's _HAS_DEPTH_MAP_ variants; fx_set_scene_depth).  A kernel argument of its own, passed
+// only to the depth instantiations (a trailing parameter pack that is empty in the others), never part of FrameConsts.
+struct DepthArgs {
+	const float* depth;    // float[H][W] of the viewport, D3D depth: 0 = near plane, 1 = far plane (nothing there)
+	int W, H;
+	float wvp[16];         // CBPerObject.WorldViewProj (Fluid.cpp:315-318: world * view * proj) as its four constant-buffer rows
+	float z_near, z_far;   // the projection's planes (UnprojectZ of the cube resolve)
+	float* cube_depth;     // the cube map's depth at the mip being marched (written) or resolved (read): float[6][S][S]
+};
+
 struct SimParams {
 	float dt;
 	int address;           // fx_address
@@ -158,11 +168,11 @@ hipError_t launch_raymarch_light(const Geom& g, int half_store, const void* colo
 	const FrameConsts& fc, const float* sh, uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr);
 hipError_t launch_raymarch_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int cube_size, uint32_t mask, uint32_t num_samples,
-	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters = nullptr);
+	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
 // direct screen-space march (row f-2): one ray per pixel, blended into the RGBA8 target (and/or kept as float4)
 hipError_t launch_raycast_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate,
-	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters = nullptr);
+	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
 // accelerated path (fx_render_accel.hip; the default, bit-identical to the plain one).  Device scratch, owned by the context:
 struct RenderAccel {
 	float* occ;          // per 4^3 block: max alpha over everything a sample based in the block can touch (n cells) + the maxima it is dilated from (n cells)
@@ -194,17 +204,18 @@ hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lig
 	uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr, bool filled = false);
 hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int cube_size, uint32_t mask, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* cube, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters = nullptr);
+	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
 hipError_t launch_accel_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* target, float* out_float, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters = nullptr);
+	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
 // 2-D visualiser (PSVisualizeColor): colour[parity] of a Z = 1 grid onto the render target
 hipError_t launch_visualize_color(const Geom& g, int half_store, const void* color, int W, int H, uint8_t* target, float* out_float, hipStream_t s);
 hipError_t launch_lightmap_decode(const uint32_t* lightmap, float* out, size_t n, hipStream_t s);
 
 // ---- cube map -> screen resolve (fx_resolve.hip; row f-1)
+// depth (optional): the depth-aware CubeCast (PSCube.hlsli:82-113), for a cube map that was marched with the same scene depth attached
 hipError_t launch_resolve_cube(const uint8_t* cube_mip, int N, const FrameConsts& fc, int W, int H, uint8_t* target,
-	float* out_float, hipStream_t s);
+	float* out_float, hipStream_t s, const DepthArgs* depth = nullptr);
 hipError_t launch_clear_target(uint8_t* target, int W, int H, const float rgba[4], hipStream_t s);
 // sky pass (PSEnvironment): float radiance cube [6][n][n][3] on the device -> target (opaque write) and/or float4
 hipError_t launch_environment(const float* cube, int n, const FrameConsts& fc, int W, int H, uint8_t* target, float* out_float, hipStream_t s);

@@ -649,6 +649,59 @@ __device__ __forceinline__ bool pixel_ray(const FrameConsts& fc, int px, int py,
 	return compute_ray_origin(o, d);                                               // :50 discard
 }
 
+// ---- scene depth (the reference's _HAS_DEPTH_MAP_ variants; fx_set_scene_depth) ------------------------------------------------
+// The view-ray kernels take a trailing parameter pack: empty (no depth -- the overloads below without a DepthArgs return what the kernels
+// passed before, so those instantiations compile to the same code) or one DepthArgs.
+//
+// GetTMax (RayMarch.hlsli:99-110): the ray parameter at which the ray meets the scene point of clip position (x, y, z), the largest of
+// the three per-axis quotients; FLT_MAX on the far plane.  dp4 = fma chain, as the other restated matrix products.
+__device__ __forceinline__ float depth_tmax(const FrameConsts& fc, float x, float y, float z, const float o[3], const float d[3])
+{
+	if (z >= 1.0f) return 3.40282347e+38f;                                         // :102
+	const float* M = fc.wvp_i;
+	float h[4];
+#pragma unroll
+	for (int r = 0; r < 4; ++r) h[r] = fmaf(1.0f, M[4 * r + 3], fmaf(z, M[4 * r + 2], fmaf(y, M[4 * r + 1], x * M[4 * r + 0])));   // :104
+	const float tx = (h[0] / h[3] + -o[0]) / d[0], ty = (h[1] / h[3] + -o[1]) / d[1], tz = (h[2] / h[3] + -o[2]) / d[2];   // :105-107
+	return fmaxf(fmaxf(tx, ty), tz);                                               // :109
+}
+
+// direct march (PSRayCast.hlsl:52-56): GetClipPos (:30-39) = the pixel's own depth texel at its screen-quad position.  Without depth the
+// shader has no `t > tMax` test at all (:119-120); FLT_MAX never passes it.
+__device__ __forceinline__ float direct_tmax(const FrameConsts&, int, int, int, int, const float*, const float*) { return 3.40282347e+38f; }
+__device__ __forceinline__ float direct_tmax(const FrameConsts& fc, int px, int py, int W, int H, const float o[3], const float d[3], const DepthArgs& da)
+{
+	const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H;
+	return depth_tmax(fc, fmaf(u, 2.0f, -1.0f), fmaf(v, -2.0f, 1.0f), da.depth[(size_t)py * W + px], o, d);
+}
+
+// nearest texel of coordinate u in [0, 1) on n texels, clamped to the edge (NaN -> 0): the point sampler of CSRayMarch.hlsl:89, which
+// the reference never creates -- this addressing is the library's choice
+__device__ __forceinline__ int depth_texel(float u, int n)
+{
+	const float f = u * (float)n;
+	return !(f >= 0.0f) ? 0 : f >= (float)n ? n - 1 : (int)f;
+}
+
+// cube-map march (CSRayMarch.hlsl:121-126): GetClipPos (:80-92) projects a point just inside the entry with the forward WorldViewProj and
+// point-samples the scene depth there; the texel's cube depth takes that value (store: the lane that writes the texel), and the march
+// ends at the nearer of the scene point and the cube-map target (RayMarch.hlsli:112-115)
+__device__ __forceinline__ float cube_tmax(const FrameConsts&, int, int, int, int, const float*, const float*, float tMax, bool) { return tMax; }
+__device__ __forceinline__ float cube_tmax(const FrameConsts& fc, int face, int x, int y, int size, const float o[3], const float d[3], float tMax, bool store,
+	const DepthArgs& da)
+{
+	const float p0 = fmaf(d[0], 0.01f, o[0]), p1 = fmaf(d[1], 0.01f, o[1]), p2 = fmaf(d[2], 0.01f, o[2]);   // :82
+	const float* M = da.wvp;
+	float h[4];
+#pragma unroll
+	for (int r = 0; r < 4; ++r) h[r] = fmaf(1.0f, M[4 * r + 3], fmaf(p2, M[4 * r + 2], fmaf(p1, M[4 * r + 1], p0 * M[4 * r + 0])));   // :83
+	const float cx = h[0] / h[3], cy = h[1] / h[3];                               // :85
+	const float u = fmaf(cx, 0.5f, 0.5f), v = -fmaf(cy, 0.5f, 0.5f) + 1.0f;        // :86-87
+	const float z = da.depth[(size_t)depth_texel(v, da.H) * da.W + depth_texel(u, da.W)];   // :89
+	if (store) da.cube_depth[((size_t)face * size + y) * size + x] = z;            // CSRayMarch.hlsl:124
+	return fminf(depth_tmax(fc, cx, cy, z, o, d), tMax);                           // :125
+}
+
 __device__ __forceinline__ uint32_t blend_premultiplied(uint32_t dd, float sr, float sg, float sb, float sa)
 {
 	const float ia = 1.0f - sa;

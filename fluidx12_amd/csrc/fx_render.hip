@@ -9,6 +9,7 @@
 //                        SEPARATE = CSRayMarchV.hlsl:5-7 (light = light-map fetch),
 //                        otherwise the merged variant with the nested light march (RayMarch.hlsli:260-294)
 //   k_raycast_direct  <- PSRayCast.hlsl:44-127 / PSRayCastV.hlsl (row f-2)
+// Both view kernels also come as the _HAS_DEPTH_MAP_ variants (a DepthArgs behind the other arguments): the march ends at the scene depth.
 // (paths relative to /root/reference/FluidX12/Content/Shaders/; the march itself lives in fx_march.h).
 // A wave64 = one 8x8 texel tile (view) or 64 consecutive x (light), so the taps of a wave are spatially coherent.
 // Light map = packed R11G11B10_FLOAT like the reference (Fluid.cpp:226), cube map = R8G8B8A8_UNORM.
@@ -45,10 +46,11 @@ __global__ __launch_bounds__(256) void k_raymarch_light(const Geom g, const type
 	flush_counts(counters, 0u, ns, 0u);
 }
 
-template <bool HALF, bool SEPARATE>
+// Dep: empty, or the scene depth (fx_march.h cube_tmax / direct_tmax)
+template <bool HALF, bool SEPARATE, class... Dep>
 __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typename ColTex<HALF>::T* __restrict__ col,
 	const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh, int size, uint32_t mask,
-	uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters)
+	uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters, const Dep... dep)
 {
 	const int face = blockIdx.z;
 	if (!((mask >> face) & 1u)) return;                                            // CSRayMarch.hlsl:102
@@ -56,6 +58,7 @@ __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typena
 	if (x >= size || y >= size) return;
 	float o[3], d[3], tMax;
 	if (!cube_texel_ray(fc, face, x, y, size, o, d, tMax)) return;                 // :116
+	tMax = cube_tmax(fc, face, x, y, size, o, d, tMax, true, dep...);              // :121-126
 	const PlainVol<HALF> vol{ col };
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
@@ -72,11 +75,11 @@ __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typena
 // taps of a wave stay spatially coherent; output = the shader's premultiplied SV_TARGET, merged into the RGBA8 target
 // with the PREMULTIPLIED blend (Fluid.cpp:670,685) and optionally kept as float4 (parity tests).
 // ---------------------------------------------------------------------------------------------------
-template <bool HALF, bool SEPARATE>
+template <bool HALF, bool SEPARATE, class... Dep>
 __global__ __launch_bounds__(64) void k_raycast_direct(const Geom g, const typename ColTex<HALF>::T* __restrict__ col,
 	const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh, int W, int H,
 	uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ target, float4* __restrict__ out_float,
-	unsigned long long* __restrict__ counters)
+	unsigned long long* __restrict__ counters, const Dep... dep)
 {
 	const int px = blockIdx.x * 8 + threadIdx.x, py = blockIdx.y * 8 + threadIdx.y;
 	if (px >= W || py >= H) return;
@@ -87,7 +90,8 @@ __global__ __launch_bounds__(64) void k_raycast_direct(const Geom g, const typen
 	const PlainVol<HALF> vol{ col };
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
-	march_ray<PlainVol<HALF>, SEPARATE, 1>(g, vol, lightmap, fc, sh, o, d, 3.40282347e+38f, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
+	const float tMax = direct_tmax(fc, px, py, W, H, o, d, dep...);                // PSRayCast.hlsl:52-56
+	march_ray<PlainVol<HALF>, SEPARATE, 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :124
 	if (out_float) out_float[pix] = make_float4(sr, sg, sb, sa);
@@ -130,12 +134,14 @@ hipError_t launch_raymarch_light(const Geom& g, int half_store, const void* colo
 
 hipError_t launch_raymarch_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int cube_size, uint32_t mask, uint32_t num_samples,
-	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters)
+	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters, const DepthArgs* depth)
 {
 	const dim3 grid((cube_size + 7) / 8, (cube_size + 7) / 8, 6), block(8, 8, 1);
 	uint32_t* out = reinterpret_cast<uint32_t*>(cube);
-#define FX_LAUNCH(H, S) hipLaunchKernelGGL((k_raymarch_view<H, S>), grid, block, 0, s, g, \
-	(const typename ColTex<H>::T*)color, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters)
+#define FX_LAUNCH(H, S) do { if (depth) hipLaunchKernelGGL((k_raymarch_view<H, S>), grid, block, 0, s, g, \
+	(const typename ColTex<H>::T*)color, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters, *depth); \
+	else hipLaunchKernelGGL((k_raymarch_view<H, S>), grid, block, 0, s, g, \
+	(const typename ColTex<H>::T*)color, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters); } while (0)
 	if (half_store) { if (separate) FX_LAUNCH(true, true); else FX_LAUNCH(true, false); }
 	else { if (separate) FX_LAUNCH(false, true); else FX_LAUNCH(false, false); }
 #undef FX_LAUNCH
@@ -144,15 +150,17 @@ hipError_t launch_raymarch_view(const Geom& g, int half_store, const void* color
 
 hipError_t launch_raycast_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate,
-	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters)
+	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters, const DepthArgs* depth)
 {
 	const dim3 grid((W + 7) / 8, (H + 7) / 8, 1), block(8, 8, 1);
-#define FX_LAUNCH(HF, S) hipLaunchKernelGGL((k_raycast_direct<HF, S>), grid, block, 0, s, g, \
-	(const typename ColTex<HF>::T*)color, lightmap, fc, sh, W, H, num_samples, num_light_samples, \
-	reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters)
+#define FX_ARGS(HF) g, (const typename ColTex<HF>::T*)color, lightmap, fc, sh, W, H, num_samples, num_light_samples, \
+	reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters
+#define FX_LAUNCH(HF, S) do { if (depth) hipLaunchKernelGGL((k_raycast_direct<HF, S>), grid, block, 0, s, FX_ARGS(HF), *depth); \
+	else hipLaunchKernelGGL((k_raycast_direct<HF, S>), grid, block, 0, s, FX_ARGS(HF)); } while (0)
 	if (half_store) { if (separate) FX_LAUNCH(true, true); else FX_LAUNCH(true, false); }
 	else { if (separate) FX_LAUNCH(false, true); else FX_LAUNCH(false, false); }
 #undef FX_LAUNCH
+#undef FX_ARGS
 	return hipGetLastError();
 }
 

@@ -706,10 +706,12 @@ __device__ __forceinline__ AccelVol<HALF, COARSE> view_volume(uint32_t* lds, con
 	return AccelVol<HALF, COARSE>{ col, alpha, occ, SEPARATE ? lds : lds + m.words, lds, m.msh, m.MX, m.MY, m.CX, m.CY };
 }
 
-template <bool HALF, bool SEPARATE, bool COARSE>
+// Dep (here and below): empty, or the scene depth (fx_march.h cube_tmax / direct_tmax)
+template <bool HALF, bool SEPARATE, bool COARSE, class... Dep>
 __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, const float* __restrict__ alpha,
 	const float* __restrict__ occ, const MaskArgs m, const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh,
-	int size, uint32_t mask, uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters)
+	int size, uint32_t mask, uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters,
+	const Dep... dep)
 {
 	extern __shared__ uint32_t lds[];
 	const int face = blockIdx.z;
@@ -718,6 +720,7 @@ __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename
 	const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
 	float o[3] = { 0.0f, 0.0f, 0.0f }, d[3] = { 0.0f, 0.0f, 1.0f }, tMax = 0.0f;
 	const bool go = x < size && y < size && cube_texel_ray(fc, face, x, y, size, o, d, tMax);   // :116
+	if (go) tMax = cube_tmax(fc, face, x, y, size, o, d, tMax, true, dep...);     // :121-126
 	const AccelVol<HALF, COARSE> vol = view_volume<HALF, SEPARATE, COARSE>(lds, col, alpha, occ, m, __syncthreads_or(go) != 0);
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
@@ -730,11 +733,11 @@ __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename
 }
 
 // direct screen-space march (row f-2; PSRayCast.hlsl:44-127 / PSRayCastV.hlsl): 16 x 16 pixels per workgroup
-template <bool HALF, bool SEPARATE, bool COARSE>
+template <bool HALF, bool SEPARATE, bool COARSE, class... Dep>
 __global__ __launch_bounds__(256) void k_direct_march(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, const float* __restrict__ alpha,
 	const float* __restrict__ occ, const MaskArgs m, const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh,
 	int W, int H, uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ target, float4* __restrict__ out_float,
-	unsigned long long* __restrict__ counters)
+	unsigned long long* __restrict__ counters, const Dep... dep)
 {
 	extern __shared__ uint32_t lds[];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -747,7 +750,8 @@ __global__ __launch_bounds__(256) void k_direct_march(const Geom g, const typena
 	const AccelVol<HALF, COARSE> vol = view_volume<HALF, SEPARATE, COARSE>(lds, col, alpha, occ, m, __syncthreads_or(go) != 0);
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
-	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1>(g, vol, lightmap, fc, sh, o, d, 3.40282347e+38f, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
+	const float tMax = go ? direct_tmax(fc, px, py, W, H, o, d, dep...) : 3.40282347e+38f;   // PSRayCast.hlsl:52-56
+	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	if (!go) return;
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :124
@@ -770,7 +774,7 @@ static const int kSlots = 8;
 static const size_t kViewWorkgroups = 1024;                    // persistent: 256 CUs x 4 (LDS: masks 32 KiB + exchange 5 KiB each)
 static const int kXchgFloats = 5 * kSlots * (64 / kSlots);       // per wave: [ray][kind, alpha, r, g, b][slot]
 
-template <bool HALF, bool COARSE>
+template <bool HALF, bool COARSE, class... Dep>
 #ifndef FX_VIEW_NT
 #define FX_VIEW_NT 256
 #endif
@@ -785,7 +789,7 @@ template <bool HALF, bool COARSE>
 __global__ __launch_bounds__(FX_VIEW_NT) FX_VIEW_ATTR void k_view_slots(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, const float* __restrict__ alpha,
 	const float* __restrict__ occ, const MaskArgs m, const uint32_t* __restrict__ lightmap, const FrameConsts fc,
 	int size, uint32_t mask, uint32_t numSamples, uint32_t* __restrict__ cube, uint32_t* __restrict__ heads,
-	unsigned long long* __restrict__ counters, int order)
+	unsigned long long* __restrict__ counters, int order, const Dep... dep)
 {
 	extern __shared__ uint32_t lds[];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane >> 3, s = lane & 7;
@@ -837,6 +841,7 @@ __global__ __launch_bounds__(FX_VIEW_NT) FX_VIEW_ATTR void k_view_slots(const Ge
 		const size_t pix = ((size_t)face * size + y) * size + x;
 		float o[3] = { 0.0f, 0.0f, 0.0f }, d[3] = { 0.0f, 0.0f, 1.0f }, tMax = 3.40282347e+38f;
 		const bool go = x < size && y < size && cube_texel_ray(fc, face, x, y, size, o, d, tMax);   // CSRayMarch.hlsl:116
+		if (go) tMax = cube_tmax(fc, face, x, y, size, o, d, tMax, s == 0, dep...);   // :121-126 (the slot replay below honours any tMax)
 
 		float sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, t = 0.0f, prev = 0.0f;
 		uint32_t i = 0;
@@ -953,7 +958,7 @@ static MaskArgs mask_args(const RenderAccel& a) { return MaskArgs{ mask_pos(a), 
 
 hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int cube_size, uint32_t mask, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* cube, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters)
+	unsigned long long* counters, const DepthArgs* depth)
 {
 	const dim3 grid((cube_size + 15) / 16, (cube_size + 15) / 16, 6), block(256);
 	const size_t lds = (size_t)a.mask_words * 4 * (separate ? 1 : 2);
@@ -968,35 +973,42 @@ hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, c
 		// the order as numbered measured better: 128^3 0.094 against 0.116 ms, 150^3 0.102 / 0.111; 256-texel cubes 0.116 / 0.102
 		const size_t visible_groups = groups / 6 * (size_t)__builtin_popcount(mask & 63u);
 		const int view_order = FX_KNOB_INT("VIEW_ORDER", visible_groups >= 6 * (size_t)pgrid.x * vw ? 1 : 0);
-#define FX_SLOTS(H, C) hipLaunchKernelGGL((k_view_slots<H, C>), pgrid, dim3(FX_VIEW_NT), plds, s, g, (const typename ColTex<H>::T*)color, a.alpha, a.occ, m, \
-	lightmap, fc, cube_size, mask, num_samples, out, ctr_now(a, g) + ctr_heads(g), counters, view_order)
+#define FX_ARGS(H) g, (const typename ColTex<H>::T*)color, a.alpha, a.occ, m, lightmap, fc, cube_size, mask, num_samples, out, ctr_now(a, g) + ctr_heads(g), counters, view_order
+#define FX_SLOTS(H, C) do { if (depth) hipLaunchKernelGGL((k_view_slots<H, C>), pgrid, dim3(FX_VIEW_NT), plds, s, FX_ARGS(H), *depth); \
+	else hipLaunchKernelGGL((k_view_slots<H, C>), pgrid, dim3(FX_VIEW_NT), plds, s, FX_ARGS(H)); } while (0)
 		if (half_store) { if (a.msh) FX_SLOTS(true, true); else FX_SLOTS(true, false); }
 		else { if (a.msh) FX_SLOTS(false, true); else FX_SLOTS(false, false); }
 #undef FX_SLOTS
+#undef FX_ARGS
 		return hipGetLastError();
 	}
-#define FX_LAUNCH(H, S, C) hipLaunchKernelGGL((k_view_march<H, S, C>), grid, block, lds, s, g, (const typename ColTex<H>::T*)color, a.alpha, a.occ, m, \
-	lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters)
+#define FX_ARGS(H) g, (const typename ColTex<H>::T*)color, a.alpha, a.occ, m, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters
+#define FX_LAUNCH(H, S, C) do { if (depth) hipLaunchKernelGGL((k_view_march<H, S, C>), grid, block, lds, s, FX_ARGS(H), *depth); \
+	else hipLaunchKernelGGL((k_view_march<H, S, C>), grid, block, lds, s, FX_ARGS(H)); } while (0)
 #define FX_PICK(H, S) do { if (a.msh) FX_LAUNCH(H, S, true); else FX_LAUNCH(H, S, false); } while (0)
 	if (half_store) FX_PICK(true, false); else FX_PICK(false, false);              // the merged march: its samples cast rays of their own
 #undef FX_LAUNCH
+#undef FX_ARGS
 	return hipGetLastError();
 }
 
 hipError_t launch_accel_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* target, float* out_float, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters)
+	unsigned long long* counters, const DepthArgs* depth)
 {
 	const dim3 grid((W + 15) / 16, (H + 15) / 16, 1), block(256);
 	const size_t lds = (size_t)a.mask_words * 4 * (separate ? 1 : 2);
 	const MaskArgs m = mask_args(a);
-#define FX_LAUNCH(HF, S, C) hipLaunchKernelGGL((k_direct_march<HF, S, C>), grid, block, lds, s, g, (const typename ColTex<HF>::T*)color, a.alpha, a.occ, m, \
-	lightmap, fc, sh, W, H, num_samples, num_light_samples, reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters)
+#define FX_ARGS(HF) g, (const typename ColTex<HF>::T*)color, a.alpha, a.occ, m, lightmap, fc, sh, W, H, num_samples, num_light_samples, \
+	reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters
+#define FX_LAUNCH(HF, S, C) do { if (depth) hipLaunchKernelGGL((k_direct_march<HF, S, C>), grid, block, lds, s, FX_ARGS(HF), *depth); \
+	else hipLaunchKernelGGL((k_direct_march<HF, S, C>), grid, block, lds, s, FX_ARGS(HF)); } while (0)
 	// one lane per pixel for both variants: two million rays, most of them beside the volume, keep every SIMD busy without the
 	// eight-lanes-per-ray scheme (measured at 1920x1080 / 256^3: 0.33 ms either way, 0.47 ms with it)
 	if (half_store) { if (separate) FX_PICK(true, true); else FX_PICK(true, false); }
 	else { if (separate) FX_PICK(false, true); else FX_PICK(false, false); }
 #undef FX_LAUNCH
+#undef FX_ARGS
 #undef FX_PICK
 	return hipGetLastError();
 }

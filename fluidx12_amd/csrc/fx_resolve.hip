@@ -3,7 +3,7 @@
 //   k_resolve_cube  <- PSRayCastCube.hlsl:20-113 (TexcoordToLocalPos, ComputeRayHit, ComputeCubeTexcoord, main)
 //                      + PSCube.hlsli:41-122 (GetDomain, CubeCast), the raster-free formulation of Fluid::renderCube
 //                      (Fluid.cpp:910-931), output merger = PREMULTIPLIED blend into an R8G8B8A8_UNORM target
-//                      (Fluid.cpp:653, FluidX12.cpp:31)
+//                      (Fluid.cpp:653, FluidX12.cpp:31); with a scene depth attached the depth-aware CubeCast (PSCube.hlsli:82-113)
 // (paths relative to /root/reference/FluidX12/Content/Shaders/).  One thread per screen pixel; a wave = 64 x 1 pixels,
 // so the target is written as coalesced 256-byte runs and neighbouring rays hit neighbouring cube texels (the cube
 // mip is <= 1.5 MiB: L2 resident).  The fixed-function TextureCube pieces (face selection, gather4 footprint, seamless
@@ -54,23 +54,60 @@ __device__ __forceinline__ float4 texel(const uint32_t* __restrict__ cube, int N
 }
 
 // texel (i, j) of face f with exactly one coordinate off the face: the adjacent face's edge texel at the same
-// position along the shared edge (seamless cube filtering)
-__device__ float4 texel_across_edge(const uint32_t* __restrict__ cube, int N, int f, int i, int j)
+// position along the shared edge (seamless cube filtering) -- its face and texel
+__device__ __forceinline__ void across_edge(int N, int f, int i, int j, int& g, int& i2, int& j2)
 {
 	const float sc = i < 0 ? -1.0f : i >= N ? 1.0f : (2.0f * (float)i + 1.0f) / (float)N - 1.0f;
 	const float tc = j < 0 ? -1.0f : j >= N ? 1.0f : (2.0f * (float)j + 1.0f) / (float)N - 1.0f;
 	float P[3];
 	face_point(P, f, sc, tc);
 	const int fa = f >> 1;
-	int g = 0;
+	g = 0;
 #pragma unroll
 	for (int a = 0; a < 3; ++a)
 		if (a != fa && fabsf(P[a]) == 1.0f) g = 2 * a + (P[a] < 0.0f ? 1 : 0);
 	float s2, t2;
 	face_coords(P, g, s2, t2);
-	const int i2 = min(max((int)floorf((0.5f * s2 + 0.5f) * (float)N), 0), N - 1);
-	const int j2 = min(max((int)floorf((0.5f * t2 + 0.5f) * (float)N), 0), N - 1);
+	i2 = min(max((int)floorf((0.5f * s2 + 0.5f) * (float)N), 0), N - 1);
+	j2 = min(max((int)floorf((0.5f * t2 + 0.5f) * (float)N), 0), N - 1);
+}
+
+__device__ float4 texel_across_edge(const uint32_t* __restrict__ cube, int N, int f, int i, int j)
+{
+	int g, i2, j2;
+	across_edge(N, f, i, j, g, i2, j2);
 	return texel(cube, N, g, i2, j2);
+}
+
+// ---- the depth-aware CubeCast (PSCube.hlsli:82-113 under _HAS_DEPTH_MAP_) ----------------------------------------------------
+// The four cube-depth taps at the colour's footprint, by the colour's rules (across an edge: the adjacent face's edge texel; off a
+// corner: the mean of the other three), turned into the per-tap depth weights max(1 - 0.5 |z_pixel - z_tap|, 0) of view-space z
+// (UnprojectZ, :31-36).  Without depth every weight is 1 (the pack is empty).
+__device__ __forceinline__ void depth_weights(float dw[4], int, int, int, int, int, int) { dw[0] = dw[1] = dw[2] = dw[3] = 1.0f; }
+__device__ __forceinline__ float unproject_z(float z, float zn, float zf) { return (zn * zf) / fmaf(z, zn - zf, zf); }   // :33-35
+__device__ __forceinline__ void depth_weights(float dw[4], int N, int f, int i0, int j0, int px, int py, const DepthArgs& da)
+{
+	float z[4];
+	int missing = -1;
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		int g = f, ii = i0 + ((k == 1 || k == 2) ? 1 : 0), jj = j0 + (k < 2 ? 1 : 0);
+		const bool oi = ii < 0 || ii >= N, oj = jj < 0 || jj >= N;
+		z[k] = 0.0f;
+		if (oi && oj) { missing = k; continue; }
+		if (oi || oj) across_edge(N, f, ii, jj, g, ii, jj);
+		z[k] = da.cube_depth[((size_t)g * N + jj) * N + ii];                       // :83
+	}
+	if (missing >= 0) {
+		float acc = 0.0f;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) if (k != missing) acc += z[k];
+#pragma unroll
+		for (int k = 0; k < 4; ++k) if (k == missing) z[k] = acc / 3.0f;
+	}
+	const float zp = unproject_z(da.depth[(size_t)py * da.W + px], da.z_near, da.z_far);   // :84,99
+#pragma unroll
+	for (int k = 0; k < 4; ++k) dw[k] = fmaxf(fmaf(-0.5f, fabsf(zp - unproject_z(z[k], da.z_near, da.z_far)), 1.0f), 0.0f);   // :107-108
 }
 
 __device__ __forceinline__ uint32_t unorm8(float v)
@@ -84,8 +121,10 @@ __device__ __forceinline__ uint32_t unorm8(float v)
 
 // wvp_i: the four constant-buffer rows of CBPerObject.WorldViewProjI.  out_float (optional): the shader's SV_TARGET
 // before the output merger, float4 per pixel, zeros where discarded (parity tests); target (optional): RGBA8, blended in place.
+// Dep: empty, or the scene depth the cube map was marched with (the depth-aware CubeCast).
+template <class... Dep>
 __global__ __launch_bounds__(256) void k_resolve_cube(const uint32_t* __restrict__ cube, int N, const FrameConsts fc,
-	int W, int H, uint32_t* __restrict__ target, float4* __restrict__ out_float)
+	int W, int H, uint32_t* __restrict__ target, float4* __restrict__ out_float, const Dep... dep)
 {
 	const int px = blockIdx.x * blockDim.x + threadIdx.x;
 	const int py = blockIdx.y * blockDim.y + threadIdx.y;
@@ -192,10 +231,14 @@ __global__ __launch_bounds__(256) void k_resolve_cube(const uint32_t* __restrict
 		du = fminf(uN, g + -0.5f) < 0.5f ? 1.0f : 0.0f;
 	}
 	const float idu = -du + 1.0f, idv = -dv + 1.0f;
-	const float wy = dv * du, wx = dv * idu, wz = du * idv, ww = idv * idu;
-	float ws = fmaf(idu, dv, wy);
-	ws = fmaf(idv, du, ws);
-	ws = fmaf(idu, idv, ws);
+	// depth weights (1 without depth: the products below are then exactly the plain CubeCast's wb, :89-95, and its weight sum)
+	float dw[4];
+	depth_weights(dw, N, f, i0, j0, px, py, dep...);
+	const float a0 = dv * dw[0], a2 = du * dw[2], a3 = idv * dw[3];
+	const float wy = dv * du * dw[1], wx = a0 * idu, wz = a2 * idv, ww = a3 * idu;
+	float ws = fmaf(idu, a0, wy);
+	ws = fmaf(idv, a2, ws);
+	ws = fmaf(idu, a3, ws);
 	float res[4];
 #define FX_CH(c, i) { float r = wy * s[1].c; r = fmaf(s[0].c, wx, r); r = fmaf(s[2].c, wz, r); r = fmaf(s[3].c, ww, r); res[i] = r / ws; }
 	FX_CH(x, 0) FX_CH(y, 1) FX_CH(z, 2) FX_CH(w, 3)
@@ -306,10 +349,12 @@ __global__ __launch_bounds__(256) void k_fill_u32(uint32_t* __restrict__ p, uint
 }
 
 hipError_t launch_resolve_cube(const uint8_t* cube_mip, int N, const FrameConsts& fc, int W, int H, uint8_t* target,
-	float* out_float, hipStream_t s)
+	float* out_float, hipStream_t s, const DepthArgs* depth)
 {
 	const dim3 block(64, 4, 1), grid((W + 63) / 64, (H + 3) / 4, 1);
-	hipLaunchKernelGGL(k_resolve_cube, grid, block, 0, s, reinterpret_cast<const uint32_t*>(cube_mip), N, fc, W, H,
+	if (depth) hipLaunchKernelGGL((k_resolve_cube<DepthArgs>), grid, block, 0, s, reinterpret_cast<const uint32_t*>(cube_mip), N, fc, W, H,
+		reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), *depth);
+	else hipLaunchKernelGGL((k_resolve_cube<>), grid, block, 0, s, reinterpret_cast<const uint32_t*>(cube_mip), N, fc, W, H,
 		reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float));
 	return hipGetLastError();
 }

@@ -178,6 +178,31 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_render_cube(self._ctx, stream, frameIndex), "RenderCube")
 
+    def SetSceneDepth(self, depth, z_near=1.0, z_far=1000.0, stream=None):
+        """the scene's depth buffer for the following renders (the reference's _HAS_DEPTH_MAP_ variants, fx_set_scene_depth):
+        float32[viewport_h][viewport_w], 0 = near plane, 1 = far plane, under the projection given to UpdateFrame, whose planes are
+        z_near / z_far.  A numpy array is copied; an object with data_ptr() on the device (a torch tensor) is read in place by every
+        later render -- this object keeps a reference to it.  None detaches."""
+        self._need()
+        if depth is None:
+            self._depth_ref = None
+            capi.check(self._lib.fx_set_scene_depth(self._ctx, stream, None, 0, 0, 0.0, 0.0, 0), "SetSceneDepth")
+            return
+        w, h = self.viewport
+        if hasattr(depth, "data_ptr") and getattr(getattr(depth, "device", None), "type", "cpu") != "cpu":
+            if tuple(depth.shape) != (h, w) or str(depth.dtype) != "torch.float32" or not depth.is_contiguous():
+                raise ValueError("device depth must be a contiguous float32[%d][%d]" % (h, w))
+            capi.check(self._lib.fx_set_scene_depth(self._ctx, stream, C.c_void_p(depth.data_ptr()), w, h, float(z_near), float(z_far),
+                                                     capi.DEPTH_DEVICE), "SetSceneDepth")
+            self._depth_ref = depth
+            return
+        a = np.ascontiguousarray(depth, np.float32)
+        if a.shape != (h, w):
+            raise ValueError("depth must be float32[%d][%d], got %s" % (h, w, a.shape))
+        capi.check(self._lib.fx_set_scene_depth(self._ctx, stream, a.ctypes.data_as(C.c_void_p), w, h, float(z_near), float(z_far), 0),
+                   "SetSceneDepth")
+        self._depth_ref = None
+
     # ---- the demo driver's time-step rule (FluidX12.cpp:266) ---------------------------------------
     def default_time_step(self):
         X, Y, Z = self.grid
@@ -231,6 +256,8 @@ class Fluid:
         if field == capi.FIELD_TARGET_FLOAT:
             return (self.viewport[1], self.viewport[0], 4), np.float32
         s = self.frame_info().cube_size
+        if field == capi.FIELD_CUBE_DEPTH:
+            return (6, s, s), np.float32
         return (6, s, s, 4), np.uint8
 
     def download(self, field):

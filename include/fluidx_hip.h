@@ -57,12 +57,15 @@ enum fx_address { FX_ADDRESS_CLAMP = 0,         /* FluidEZ.cpp:406 (default path
  *   PRESSURE  float[Z][Y][X]     (m_incompress)      DIVERGENCE float[Z][Y][X] (scratch b)
  *   LIGHTMAP  float[Z][Y][X][3]  (m_lightMap decoded from R11G11B10F)
  *   CUBEMAP   uint8[6][S][S][4]  (mip `lod` of m_cubeMap, S = X >> lod, R8G8B8A8_UNORM)
+ *   CUBE_DEPTH float[6][S][S]    (mip `lod` of the cube depth: the scene depth each texel's ray saw when the last cube-path fx_render ran
+ *                                with a depth attached, CSRayMarch.hlsl:124; 1.0 where no such ray was cast; download only)
  * Z = the context's own slab (slab_nz planes), never the halo. */
 enum fx_field {
 	FX_FIELD_VELOCITY = 0, FX_FIELD_VELOCITY1 = 1, FX_FIELD_COLOR = 2, FX_FIELD_COLOR_PREV = 3,
 	FX_FIELD_PRESSURE = 4, FX_FIELD_DIVERGENCE = 5, FX_FIELD_LIGHTMAP = 6, FX_FIELD_CUBEMAP = 7,
 	FX_FIELD_TARGET = 8,        /* render target of fx_render_cube: uint8 [viewport_h][viewport_w][4] (download only) */
-	FX_FIELD_TARGET_FLOAT = 9   /* the resolve's output before the blend: float [h][w][4], zeros where discarded     */
+	FX_FIELD_TARGET_FLOAT = 9,  /* the resolve's output before the blend: float [h][w][4], zeros where discarded     */
+	FX_FIELD_CUBE_DEPTH = 10    /* see above (3-D contexts with a viewport)                                          */
 };
 
 typedef struct fx_ctx fx_ctx;
@@ -168,6 +171,23 @@ int fx_render(fx_ctx* ctx, void* stream, uint8_t frame_index, uint8_t flags);
  * the PREMULTIPLIED blend (Fluid.cpp:653).  Read the result with fx_download(FX_FIELD_TARGET). */
 int fx_clear_render_target(fx_ctx* ctx, void* stream, const float rgba[4]);
 int fx_render_cube(fx_ctx* ctx, void* stream, uint8_t frame_index);
+
+/* Scene depth for the following renders (the reference's _HAS_DEPTH_MAP_ variants): the volume is occluded by the scene it stands in.
+ * depth = float[viewport_h][viewport_w], D3D convention: 0 = near plane, 1 = far plane = "nothing here" (the demo's clear value,
+ * FluidX12.cpp:473), under the projection passed to fx_update_frame.  z_near / z_far: that projection's planes (SharedConsts.h:8-9: 1, 1000),
+ * used by the cube resolve's UnprojectZ.  flags & FX_DEPTH_DEVICE: `depth` is device memory of the context's device, read in place by every
+ * later render (the caller keeps it alive and orders its writes on `stream`); otherwise it is copied, enqueued on `stream`, and the call
+ * returns once the copy is made.  NULL detaches: renders are then exactly what they are without this call.
+ *   direct march (PSRayCast.hlsl:52-56)   every ray ends at its pixel's scene point (GetTMax, RayMarch.hlsli:99-110)
+ *   cube-map march (CSRayMarch.hlsl:121-126)  each texel's ray point-samples the depth (nearest texel, clamped to the edge) where a point just
+ *                                         inside its entry projects, ends there, and keeps the value in FX_FIELD_CUBE_DEPTH
+ *   fx_render_cube (PSCube.hlsli:82-113)   weights the four cube taps by view-space depth agreement with the pixel, when the cube map
+ *                                         resolved was marched with depth attached
+ * Depth is render state: kept across fx_update_frame, not checkpointed, not digested; FX_FLAG_RENDER_ONLY contexts take it too.
+ * FX_E_INVALID: size is not the viewport, 2-D grid, 0 x 0 viewport, slab context, !(0 < z_near < z_far), unknown flag bits. */
+#define FX_DEPTH_DEVICE 0x1u
+int fx_set_scene_depth(fx_ctx* ctx, void* stream, const float* depth, uint32_t width, uint32_t height,
+	float z_near, float z_far, uint32_t flags);
 
 /* The light probe's sky pass (LightProbe::RenderEnvironment, LightProbe.cpp:85-97; PSEnvironment.hlsl), which the demo draws
  * before the volume (FluidX12.cpp:483): fx_set_environment keeps a copy of the radiance cube float[6][n][n][3] on the device

@@ -2,6 +2,11 @@
 library's own HIP-event marks.  Run on the GPU box (optionally under tools/kstats.sh for per-kernel times):
 
     python3 tools/render_bench.py [--grid 256] [--frame 132] [--storage fp32] [--sh] [--reps 5] [--modes 1,0] [--flags optimized,merged,direct]
+                                  [--depth none|far|plane]
+
+--depth attaches a scene depth (fx_set_scene_depth): `far` a cleared buffer (1.0: nothing occludes), `plane` the fronto-parallel plane through
+the volume's centre, which cuts the plume in half.  Each run also reports the view rays' colour samples of one counted render
+(FX_OPT_COUNT_SAMPLES, outside the timed renders).
 """
 import argparse
 import json
@@ -25,6 +30,7 @@ def main():
     ap.add_argument("--modes", default="1,0")
     ap.add_argument("--flags", default="optimized")
     ap.add_argument("--viewport", default="1920x1080")
+    ap.add_argument("--depth", default="none", choices=("none", "far", "plane"))
     a = ap.parse_args()
     W, H = (int(v) for v in a.viewport.split("x"))
     G = a.grid
@@ -40,10 +46,15 @@ def main():
         sh = (np.random.default_rng(5).random((9, 3)) * np.array([[2.0]] + [[0.5]] * 8)).astype(np.float32)
         f.SetSH(sh)
     f.UpdateFrame(0.0, 0, view, proj, eye)
+    if a.depth != "none":
+        P = np.asarray(proj, np.float64).reshape(4, 4)
+        zv = float(np.linalg.norm(eye))                 # the camera looks at the volume's centre: view-space z of the plane through it
+        z = 1.0 if a.depth == "far" else P[2, 2] + P[3, 2] / zv
+        f.SetSceneDepth(np.full((H, W), z, np.float32))
     f.Synchronize()
     flagmap = {"optimized": fx.Fluid.OPTIMIZED, "merged": fx.Fluid.RAY_MARCH_CUBEMAP, "direct": fx.Fluid.SEPARATE_LIGHT_PASS,
                "direct_merged": fx.Fluid.RAY_MARCH_DIRECT}
-    out = {"grid": G, "frame": a.frame, "storage": a.storage, "sh": a.sh, "runs": []}
+    out = {"grid": G, "frame": a.frame, "storage": a.storage, "sh": a.sh, "depth": a.depth, "runs": []}
     pics = {}
     for mode in (int(m) for m in a.modes.split(",")):
         f.set_option(capi.OPT_RENDER_ACCEL, mode)
@@ -55,6 +66,14 @@ def main():
             key = (name,)
             pic = (f.download(fx.FIELD_LIGHTMAP).tobytes() if fl & fx.Fluid.SEPARATE_LIGHT_PASS else b"") + \
                 (f.download(fx.FIELD_CUBEMAP).tobytes() if fl & fx.Fluid.RAY_MARCH_CUBEMAP else f.download(fx.FIELD_TARGET_FLOAT).tobytes())
+            f.set_option(capi.OPT_COUNT_SAMPLES, 1)
+            f.timing_enable(True)
+            f.timing_read(reset=True)
+            f.Render(0, fl)
+            f.Synchronize()
+            view_samples = f.timing_read(reset=True).view_samples
+            f.set_option(capi.OPT_COUNT_SAMPLES, 0)
+            f.timing_enable(False)
             same = None
             if key in pics:
                 same = pics[key] == pic
@@ -67,7 +86,7 @@ def main():
             t = f.timing_read(reset=True)
             f.timing_enable(False)
             out["runs"].append({"accel": mode, "flags": name, "light_ms": t.light_ms / a.reps, "view_ms": t.view_ms / a.reps,
-                                "same_picture_as_first_mode": same})
+                                "view_samples": view_samples, "same_picture_as_first_mode": same})
     print(json.dumps(out, indent=1))
 
 
