@@ -76,11 +76,6 @@ hipError_t launch_jacobi_sweep(const Geom& g, const float* p_in, const float* b,
 // the same sweep over two disjoint plane ranges in one launch (the two face zones of a slab)
 hipError_t launch_jacobi_sweep2(const Geom& g, const float* p_in, const float* b, float* p_out, uint8_t* frozen,
 	int z_begin, int z_end, int z_begin2, int z_end2, hipStream_t s);
-// `sweeps` lock-step sweeps fused in one launch (temporal blocking); result in p_out.  Planes [z_begin, z_end)
-// of p_out are valid afterwards provided p_in/b are valid on [z_begin - sweeps, z_end + sweeps) (or the
-// global boundary).  Returns hipErrorNotSupported when the geometry has no fused path.
-hipError_t launch_jacobi_fused(const Geom& g, const float* p_in, const float* b, float* p_out, int sweeps,
-	int z_begin, int z_end, hipStream_t s);
 // two or three sweeps per launch, register-resident strips (fx_jacobi_strip.hip)
 bool jacobi_strip_supported(const Geom& g);
 bool jacobi_strip_wide(const Geom& g);       // X = 512: only the two-sweep wide kernel exists
@@ -133,10 +128,22 @@ hipError_t launch_freeze_strip4(const Geom& g, const float* p_in, const float* b
 // 2-D grids (fx_jacobi2d.hip): up to jacobi2d_max_sweeps (0: not a 2-D grid / switched off) lock-step sweeps per launch on LDS tiles, with or without the freeze bytes
 int jacobi2d_max_sweeps(const Geom& g);
 hipError_t launch_jacobi2d(const Geom& g, const float* p_in, const float* b, float* p_out, const uint8_t* frozen_in, uint8_t* frozen_out, int sweeps, hipStream_t s);
-// sweeps fused per launch for this geometry (1 = no fused path); requested > 0 overrides the default
-int jacobi_fused_max_sweeps(const Geom& g, int requested, int nzp);
-bool jacobi_prefers_three(const Geom& g, int requested, int nzp);
-bool jacobi_prefers_four(const Geom& g, int requested, int nzp);
+// ---- which family runs a round of the fixed-count solve, and with how many sweeps per launch (fx_jacobi_plan.cpp: the one place that decides)
+enum JacobiFamily { JF_NONE = 0, JF_SWEEP1, JF_TILE2D, JF_STRIP, JF_STRIP3, JF_STRIP4, JF_BLOCK2, JF_BLOCKG };    // one per launcher above
+struct JacobiLaunch { int family, sweeps; };
+// what a geometry runs under a jacobi_fuse request (0: none), the launcher switches, a freeze byte mask and (2-D) a second buffer for it:
+// fam[k] = the family of a launch of k sweeps, k = 1 .. 4 (JF_NONE: no such kernel; 2-D tiles: every length up to `unit`), unit = sweeps per
+// launch unless three / four (the measured preferences of the default schedule) say otherwise
+struct JacobiPolicy { int fam[5]; int unit, three, four; };
+JacobiPolicy jacobi_policy(const Geom& g, int fuse, bool frozen, bool second_mask);
+int jacobi_plan(const JacobiPolicy& p, int n, JacobiLaunch* out);        // the launches of a serial round of n sweeps, in order (at most n) -> how many
+// one planned launch, p_in -> p_out on planes [z_begin, z_end): valid provided p_in / b are valid `sweeps` planes beyond the range (or up to the
+// global boundary).  frozen: the byte mask (or null); frozen_out: where the 2-D tiles leave it
+hipError_t launch_jacobi(const Geom& g, JacobiLaunch l, const float* p_in, const float* b, float* p_out, uint8_t* frozen, uint8_t* frozen_out,
+	int z_begin, int z_end, hipStream_t s);
+// the interior launches of an overlapped round of n slab ranks: sweeps per launch, and the lengths of a round of cnt sweeps (at most cnt)
+int jacobi_group_sweeps(const JacobiPolicy* p, int n);
+int jacobi_group_parts(const JacobiPolicy& lead, int t, int cnt, int* parts);
 // The LDS hand-overs of the strip kernels wait in bounded loops; a wait that runs out raises a device word (per translation unit) instead
 // of hanging the device or continuing silently.  Read-and-clear on the current device; fx_synchronize turns a raised word into FX_E_DEVICE.
 // fx_field_digest's kernel: two wrapping sums of 64-bit mixes of (stored bits, key0 + element index) over `count` elements, added to out[0..1]

@@ -290,62 +290,38 @@ int divergence_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
-// t lock-step sweeps p[src] -> p[src ^ 1] on planes [r.lo, r.hi) in ONE launch
-// 2-D grids relax on LDS tiles (fx_jacobi2d.hip) unless the caller asked for one sweep per launch (jacobi_fuse = 1: the plainest kernels,
-// what the kernel-against-kernel parity tests compare with)
-static bool takes_2d_tiles(const fx_ctx* c) { return jacobi2d_max_sweeps(c->g) > 0 && (c->desc.flags & FX_FLAG_JACOBI_FUSE_MASK) != 1 && (!c->frozen || c->frozen_alt); }
+// what this context's rounds run (fx_jacobi_plan.cpp); asks whether a second mask buffer EXISTS, not which of the two is current (jacobi_launch swaps them)
+static JacobiPolicy policy_of(const fx_ctx* c)
+{
+	return jacobi_policy(c->g, (int)(c->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), c->frozen != nullptr, c->frozen_alt != nullptr);
+}
 
-static int jacobi_launch(fx_ctx* ctx, hipStream_t s, int src, int t, Range r, ScopedMark* mk)
+// one planned launch: l.sweeps lock-step sweeps p[src] -> p[src ^ 1] on planes [r.lo, r.hi)
+static int jacobi_launch(fx_ctx* ctx, hipStream_t s, int src, JacobiLaunch l, Range r, ScopedMark* mk)
 {
 	r.lo = std::max(r.lo, 0); r.hi = std::min(r.hi, ctx->g.Zg);
 	if (r.hi <= r.lo) return FX_OK;
 	DeviceGuard dg(ctx->device);
-	if (takes_2d_tiles(ctx)) {                             // 2-D grids: up to eight sweeps per launch on LDS tiles, freeze bytes included
-		FX_HIP(launch_jacobi2d(ctx->g, ctx->p[src], ctx->b, ctx->p[src ^ 1], ctx->frozen, ctx->frozen ? ctx->frozen_alt : nullptr, t, s));
-		if (ctx->frozen) std::swap(ctx->frozen, ctx->frozen_alt);       // the mask ping-pongs with the pressure
-	} else if (t > 1) {
-		FX_HIP(launch_jacobi_fused(ctx->g, ctx->p[src], ctx->b, ctx->p[src ^ 1], t, r.lo, r.hi, s));
-	} else {
-		FX_HIP(launch_jacobi_sweep(ctx->g, ctx->p[src], ctx->b, ctx->p[src ^ 1], ctx->frozen, r.lo, r.hi, s));
-	}
-	if (mk) { mk->launches += 1; mk->sweeps += t; }
+	FX_HIP(launch_jacobi(ctx->g, l, ctx->p[src], ctx->b, ctx->p[src ^ 1], ctx->frozen, ctx->frozen ? ctx->frozen_alt : nullptr, r.lo, r.hi, s));
+	if (l.family == JF_TILE2D && ctx->frozen) std::swap(ctx->frozen, ctx->frozen_alt);       // the mask ping-pongs with the pressure
+	if (mk) { mk->launches += 1; mk->sweeps += l.sweeps; }
 	return FX_OK;
-}
-
-// a launch of `t` sweeps the geometry has a kernel for: threes exist for X = 256 / 512 only, twos wherever a fused kernel serves the rows
-static int legal_sweeps(const fx_ctx* c, int t)
-{
-	if (c->frozen || takes_2d_tiles(c)) return t;
-	if (t == 3 && !jacobi_strip3_supported(c->g)) t = 2;
-	if (t == 2 && jacobi_fused_max_sweeps(c->g, 2, c->g.nz) < 2) t = 1;
-	return t;
-}
-
-static int fused_sweeps(const fx_ctx* c)
-{
-	if (takes_2d_tiles(c)) return jacobi2d_max_sweeps(c->g);
-	return c->frozen ? 1 : jacobi_fused_max_sweeps(c->g, (int)(c->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), c->g.nz);
 }
 
 // `count` lock-step sweeps whose first one may read `count` exchanged halo planes; the planes swept shrink by
 // one per sweep towards the owned range (redundant halo work instead of an exchange per sweep)
 static int jacobi_round(fx_ctx* ctx, hipStream_t s, int count, ScopedMark* mk)
 {
-	int done = 0;
-	while (done < count) {
-		const int left = count - done;
-		int t = std::min(left, fused_sweeps(ctx));
-		if (!ctx->frozen && !takes_2d_tiles(ctx) && jacobi_prefers_three(ctx->g, (int)(ctx->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), ctx->g.nz))
-			t = left == 4 ? 2 : std::min(left, 3);           // threes, and a remainder of 4 as 2 + 2 rather than 3 + 1
-		if (!ctx->frozen && !takes_2d_tiles(ctx) && jacobi_prefers_four(ctx->g, (int)(ctx->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), ctx->g.nz))
-			t = jacobi_strip3_supported(ctx->g) ? (left >= 7 || left == 4 ? 4 : std::min(left, 3))   // fours; a remainder of 5 / 6 as 3 + 2 / 3 + 3
-				: std::min(left, 4);                                    // (x tiles: no threes -- 4 + 2, 4 + 1)
-		t = legal_sweeps(ctx, t);
+	std::vector<JacobiLaunch> plan(count);
+	plan.resize(jacobi_plan(policy_of(ctx), count, plan.data()));
+	int left = count;
+	for (const JacobiLaunch& l : plan) {
+		const int t = l.sweeps;
 		if (mk && mk->kind == MK_JACOBI && mk->launches && t * mk->launches < mk->sweeps) mk->split(MK_JACOBI_TAIL);   // shorter launches from here on
-		const int rc = jacobi_launch(ctx, s, ctx->p_cur, t, grown(ctx, multi_rank(ctx) ? left - t : 0), mk);
+		left -= t;
+		const int rc = jacobi_launch(ctx, s, ctx->p_cur, l, grown(ctx, multi_rank(ctx) ? left : 0), mk);
 		if (rc) return rc;
 		ctx->p_cur ^= 1;
-		done += t;
 	}
 	return FX_OK;
 }
@@ -570,7 +546,8 @@ static int jacobi_serial(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, u
 // Per round the critical path is max(interior, chain + link) instead of chain + max(interior, link).  Every cell gets the
 // arithmetic of the single-domain sweep; (cell, level) pairs of the zone borders are computed twice, which is why the
 // faithful mode (its freeze mask is a side effect) takes the serial schedule instead.
-static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters, int t, int k)
+// pol: the lead's policy, then every member's; t = jacobi_group_sweeps of them
+static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters, const std::vector<JacobiPolicy>& pol, int t, int k)
 {
 	fx_comm_group* grp = lead->group;
 	int rc;
@@ -586,12 +563,9 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 	uint32_t done = 0;
 	while (done < iters) {
 		const int cnt = (int)std::min<uint32_t>(k, iters - done);
-		// the interior's launches: the remainder first, then whole t's -- each one a launch the geometry has a kernel for (the same list on
-		// every member: X and Y are the chain's)
-		std::vector<int> parts;
-		for (int left = cnt - (cnt / t) * t; left > 0;) { const int p = legal_sweeps(lead, left); parts.push_back(p); left -= p; }
-		for (int j = 0; j < cnt / t; ++j) parts.push_back(t);
-		const int m = (int)parts.size();
+		// the interior's launches: the remainder first, then whole t's (jacobi_group_parts: the same list on every member)
+		std::vector<int> parts(cnt);
+		const int m = jacobi_group_parts(pol[0], t, cnt, parts.data());
 		// (every member from ITS OWN current buffer: members that ran serial rounds before -- the schedule is an option at run time -- may
 		// hold their pressure in different buffers; SRC / FIN below are per member)
 		const int flip = m & 1;
@@ -626,7 +600,8 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 		if ((rc = comm_mark_done(lead, M, s))) return rc;
 		in_flight = true;
 		// ---- compute stream: the interior
-		for (fx_ctx* mctx : M) {
+		for (size_t i = 0; i < M.size(); ++i) {
+			fx_ctx* mctx = M[i];
 			ScopedMark mk(mctx, CS(mctx, s), MK_JACOBI);
 			const Range o = owned(mctx);
 			int lvl = 0, cur = FX_SRC(mctx);
@@ -639,7 +614,7 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 					DeviceGuard dg(mctx->device);
 					FX_HIP(hipStreamWaitEvent(CS(mctx, s), grp->lane_of(mctx).ev_face1, 0));
 				}
-				if ((rc = jacobi_launch(mctx, CS(mctx, s), cur, tj, in, &mk))) return rc;
+				if ((rc = jacobi_launch(mctx, CS(mctx, s), cur, JacobiLaunch{ pol[i + 1].fam[std::min(tj, 4)], tj }, in, &mk))) return rc;
 				cur ^= 1;
 			}
 		}
@@ -667,20 +642,13 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters)
 {
 	if (overlap_level(lead) >= 2) {
-		int t = fused_sweeps(lead);
-		bool three = true, four = true;
-		for (fx_ctx* m : M) {
-			t = std::min(t, fused_sweeps(m));
-			three = three && !m->frozen && jacobi_prefers_three(m->g, (int)(m->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), m->g.nz);
-			four = four && !m->frozen && jacobi_prefers_four(m->g, (int)(m->desc.flags & FX_FLAG_JACOBI_FUSE_MASK), m->g.nz);
-		}
-		if (three) t = 3;                              // the interior launches of a round as threes (k = 9: 3 + 3 + 3); local choice, the exchanges do not depend on it
-		if (four) t = 4;                               // ... as fours where the four-sweep kernel serves the slab (k = 9: 1 + 4 + 4)
+		std::vector<JacobiPolicy> pol{ policy_of(lead) };
+		for (fx_ctx* m : M) pol.push_back(policy_of(m));
 		const int k = lead->opt_round;
 		// two face zones (<= 2k - 1 planes each) and an interior; decided on the thinnest slab of the chain and on the (chain-wide)
 		// Jacobi mode, so that every rank takes the same branch -- the two schedules exchange different things
 		const bool ok = lead->group->lanes[0].face != nullptr && lead->group->min_nz >= 4 * k && lead->p_face[0] && !lead->frozen;
-		if (ok) return jacobi_overlapped(lead, M, s, iters, t, k);
+		if (ok) return jacobi_overlapped(lead, M, s, iters, pol, jacobi_group_sweeps(pol.data(), (int)pol.size()), k);
 	}
 	return jacobi_serial(lead, M, s, iters);
 }

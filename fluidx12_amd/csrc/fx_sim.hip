@@ -980,124 +980,6 @@ hipError_t launch_jacobi_sweep2(const Geom& g, const float* p_in, const float* b
 	return hipGetLastError();
 }
 
-// ---- temporal blocking: which geometry fuses how many sweeps ----------------------------------------
-// FLUIDX_JACOBI_T (1..3) overrides the sweeps fused per launch (measurement knob, DESIGN.md / profiles/).
-// (The LDS tile kernel k_jacobi_tb<T> of round 1 -- z-streaming register windows + one LDS plane per level, two barriers per plane --
-// lost to the register strips in every shape measured, profiles/archive/r01_jacobi_tile_sweep.txt, and was removed in round 3; with it went
-// four sweeps per launch: jacobi_fuse = 4 now runs threes.)
-
-static bool tb_supported(const Geom& g)
-{
-	const int LX = g.X >> 2;
-	return g.Zg > 1 && (g.X & 3) == 0 && (LX == 16 || LX == 32 || LX == 64) && g.Y >= 16;
-}
-
-// where two sweeps per launch (register strips) beat one: measured on MI355X with the DPP lane shifts in place
-// (us per sweep, one / two sweeps per launch): 256^3 30 / 17.8, 512x512x64 41 / 18.9, 512x512x32 21.8 / 12.0, 512x512x16
-// 12.5 / 9.9, 256x256x64 10.0 / 9.0 -- but 256x256x32 6.2 / 8.2, 128^3 5.7 / 7.6, 128x128x32 3.3 / 7.8, 64^3 2.8 / 7.3: below
-// ~4 M cells a launch is too short for 8-plane z chunks to fill the chip
-static bool strip_profitable(const Geom& g, int nzp)
-{
-	if (!jacobi_strip_supported(g)) return false;
-	return (size_t)g.X * g.Y * (size_t)nzp >= ((size_t)7 << 19);           // 3.5 M cells
-}
-
-int jacobi_fused_max_sweeps(const Geom& g, int requested, int nzp)
-{
-	const int forced = FX_KNOB_INT("JACOBI_T", 0);
-	if (jacobi_strip_supported(g) && jacobi_strip_wide(g)) {            // X = 512: one fused shape (two sweeps, wide strips)
-		const int want = requested > 0 ? requested : (forced > 0 ? forced : (strip_profitable(g, nzp) ? 2 : 1));
-		if (want >= 4 && jacobi_strip4_supported(g) && nzp >= 2) return 4;     // four sweeps: the half-row octet (k_jacobi_strip4x, fx_jacobi_strip4.hip)
-		return want >= 3 && jacobi_strip3_supported(g) ? 3 : (want >= 2 ? 2 : 1);
-	}
-	// any other row of whole quads longer than 256 cells: FOUR sweeps on x tiles of the octet (k_jacobi_strip4t, fx_jacobi_strip4.hip) where
-	// asked for or preferred (jacobi_prefers_four); remainders through the paths below
-	if (!tb_supported(g) && (requested >= 4 || (!requested && forced >= 4)) && jacobi_strip4_supported(g) && nzp >= 2) return 4;
-	// rows that fit no strip / tile kernel (X no multiple of 4, or not 64 / 128 / 256 wide): the general block-per-wave kernel, two
-	// sweeps per launch (fx_jacobi_block.hip; 150^3, the reference's GI preset: 19.3 us per single-sweep launch before)
-	if (!tb_supported(g)) return jacobi_blockg_supported(g) && (!requested || requested == 2) && !forced && nzp >= 2 ? 2 : 1;   // (requested == 2: the slab rounds)
-	// X = 128: a 4 x 4-row block per wave, two sweeps (fx_jacobi_block.hip) -- the strips have too few waves there.  (Round 6 built FOUR
-	// sweeps per launch on 8 x 8-row tiles, a workgroup each with the 16 x 16-row cone in its waves' registers and the planes handed over
-	// through the LDS: bit-exact, 24.9 us per launch against 2 x 6.8 -- eight barrier phases on one workgroup per CU; docs/LAB.md section 12.)
-	if (jacobi_block2_supported(g) && !requested && !forced) return nzp >= 2 ? 2 : 1;
-	// default: two sweeps per launch in the register-strip kernel (fx_jacobi_strip.hip) where the geometry allows it,
-	// else one sweep per launch
-	const int t = requested > 0 ? requested : (forced > 0 ? forced : (strip_profitable(g, nzp) ? 2 : 1));
-	if (t >= 4 && jacobi_strip4_supported(g) && nzp >= 2) return 4;     // four sweeps: the quad kernel (fx_jacobi_strip4.hip)
-	return t < 1 ? 1 : (t > 3 ? 3 : t);
-}
-
-// FOUR sweeps per launch (fx_jacobi_strip4.hip) where the kernels exist: 40 sweeps = 10 launches.  With the octet kernel (k_jacobi_strip4o,
-// the default) from 24 planes of 256 x 256 -- round 5, us per sweep at 256 x 256 x D in ones / twos / threes / fours: D = 24 5.7 / 7.4 / 6.8 / 5.3,
-// 32 6.2 / 7.7 / 6.9 / 5.2, 64 9.6 / 8.1 / 7.3 / 5.6, 96 - / - / 7.7 / 6.1, 128 8.8 (threes) / 7.1, 192 11.3 / 9.6, 256 14.0 / 12.1, 400 23.3 / 19.0;
-// with the quad kernel (STRIP4_OCTET=0) from 144 planes.  JACOBI_PREFER4=0 keeps the threes; an explicit jacobi_fuse / JACOBI_T request is
-// always honoured as given.
-static size_t jacobi_tiled_four_from() { return (size_t)FX_KNOB_INT("STRIP4T_FROM", 1 << 20); }
-bool jacobi_prefers_four(const Geom& g, int requested, int nzp)
-{
-	const int forced = FX_KNOB_INT("JACOBI_T", 0);
-	const int prefer = FX_KNOB_INT("JACOBI_PREFER4", 1);
-	const bool octet = FX_KNOB_INT("STRIP4_OCTET", 1) != 0;
-	if (g.X == 512)                                                     // k_jacobi_strip4x from 96 planes; below, three x tiles of the octet (k_jacobi_strip4t) from SIX planes --
-		// us per sweep at 512 x 512 x D, the round-5 schedule (ones below 16 planes, twos) / fours: 4 6.9 / 9.6, 6 7.0 / 4.9, 8 7.7 / 4.9, 12 10.1 / 5.5,
-		// 16 10.2 / 6.3, 32 12.2 / 9.3, 48 15.8 / 12.3 (rows the octet's bands cannot be placed on, Y = 15, 16: from 64 planes, k_jacobi_strip4x)
-		return prefer && !requested && !forced && jacobi_strip4_supported(g) && (size_t)g.X * g.Y * (size_t)nzp >= (g.Y >= 17 ? (size_t)3 << 19 : (size_t)1 << 24);
-	if (g.X != 256)                                                     // k_jacobi_strip4t (x tiles of the octet): see the table at jacobi_tiled_four_from
-		// (rows below 256 cells: a tile with its upper lanes switched off -- from 160 cells a row and 3.1 M cells; us per sweep, the block kernel's twos /
-		// fours: 132^3 4.9 / 5.5, 160^3 7.7 / 6.2, 192^3 9.8 / 7.7, 224^3 15.2 / 9.6, 252^3 20.3 / 11.8; 192 x 192 x 48 4.0 / 5.5,
-		// x 80 5.2 / 5.3, x 100 6.5 / 5.8; 224 x 224 x 48 4.1 / 5.6, x 64 5.8 / 5.2; 240 x 240 x 48 4.6 / 5.0, x 64 6.2 / 5.4; 160 x 160 x 100 5.1 / 5.3, x 128 6.1 / 5.9)
-		return prefer && !requested && !forced && jacobi_strip4_supported(g) &&
-			(g.X > 256 ? (size_t)g.X * g.Y * (size_t)nzp >= jacobi_tiled_four_from()
-			           : g.X >= FX_KNOB_INT("STRIP4T_NARROW", 160) && (size_t)g.X * g.Y * (size_t)nzp >= (size_t)FX_KNOB_INT("STRIP4T_NARROW_FROM", 3 << 20));
-	return prefer && !requested && !forced && jacobi_strip4_supported(g) && (size_t)g.X * g.Y * (size_t)nzp >= (octet ? (size_t)3 << 17 : (size_t)9 << 20);
-	// (the octet from SIX planes of 256 x 256 since its z chunks may be four planes short -- round 6, us per sweep in ones / fours: D = 6 3.88 / 3.33,
-	// 8 4.30 / 3.48, 12 4.79 / 3.90, 16 5.33 / 3.96, 20 5.58 / 3.87; with chunks of eight or more the fours started at 24 planes)
-}
-
-// Default schedule of the serial rounds (single domain, and slab ranks thick enough): THREE sweeps per launch (k_jacobi_strip3) where that kernel exists and the grid is large
-// enough, the remainder as two-sweep launches (40 = 12 x 3 + 2 x 2).  Measured 256^3: Jacobi stage of the bench 0.664 ms
-// against 0.714 ms in twos (15.0 against 14.3 G voxel-updates/s).  FLUIDX_JACOBI_PREFER3=0 keeps two sweeps per launch throughout; an explicit jacobi_fuse / FLUIDX_JACOBI_T
-// request is always honoured as given.
-bool jacobi_prefers_three(const Geom& g, int requested, int nzp)
-{
-	const int forced = FX_KNOB_INT("JACOBI_T", 0);
-	const int prefer = FX_KNOB_INT("JACOBI_PREFER3", 1);
-	const int no_lds3 = FX_KNOB_INT("STRIP3_OFF", 0);
-	return prefer && !requested && !forced && !no_lds3 && jacobi_strip3_supported(g) &&
-		(size_t)g.X * g.Y * (size_t)nzp >= (g.X == 512 ? (size_t)1 << 24 : (size_t)7 << 19);
-	// X = 256 (k_jacobi_strip3c): wherever the strips pay at all -- round 5, us per sweep in twos / threes / fours: 256 x 256 x 64 8.1 / 7.2 / 7.5,
-	// x 96 9.0 / 7.8 / 7.9, x 128 10.8 / 8.9 / 8.9, x 192 14.2 / 11.3 / 11.1 (the 12.6 M-cell threshold dated from the kernel before the
-	// cooperative pairs).  X = 512 (k_jacobi_strip3h): from 16.8 M cells since the round-2 hand-over order -- 512x512x64 (a rank of
-	// BASELINE configs[3]) 18.7 against 19.5 us per sweep, 512x512x128 36.2 against 43.7, 512^3 117.6 against 152 (before: 20.3 / 39.6 / 129)
-}
-
-hipError_t launch_jacobi_fused(const Geom& g, const float* p_in, const float* b, float* p_out, int sweeps,
-	int z_begin, int z_end, hipStream_t s)
-{
-	if (z_end <= z_begin) return hipSuccess;
-	if (jacobi_strip_supported(g) && jacobi_strip_wide(g)) {
-		if (sweeps == 4) return launch_jacobi_strip4(g, p_in, b, p_out, z_begin, z_end, s);
-		if (sweeps == 3 && jacobi_strip3_supported(g)) return launch_jacobi_strip3(g, p_in, b, p_out, z_begin, z_end, s);
-		return sweeps == 2 ? launch_jacobi_strip(g, p_in, b, p_out, 2, z_begin, z_end, s) : hipErrorNotSupported;
-	}
-	if (!tb_supported(g)) {
-		if (sweeps == 4) return launch_jacobi_strip4(g, p_in, b, p_out, z_begin, z_end, s);       // k_jacobi_strip4t
-		return sweeps == 2 && jacobi_blockg_supported(g) ? launch_jacobi_blockg(g, p_in, b, p_out, z_begin, z_end, s) : hipErrorNotSupported;
-	}
-	switch (sweeps) {
-	case 2:
-		if (jacobi_block2_supported(g)) return launch_jacobi_block2(g, p_in, b, p_out, z_begin, z_end, s);
-		return launch_jacobi_strip(g, p_in, b, p_out, 2, z_begin, z_end, s);
-	case 3: {
-		const int no_lds3 = FX_KNOB_INT("STRIP3_OFF", 0);    // 1 = the all-register three-sweep strips
-		if (!no_lds3 && jacobi_strip3_supported(g)) return launch_jacobi_strip3(g, p_in, b, p_out, z_begin, z_end, s);
-		return launch_jacobi_strip(g, p_in, b, p_out, 3, z_begin, z_end, s);
-	}
-	case 4: return launch_jacobi_strip4(g, p_in, b, p_out, z_begin, z_end, s);     // (hipErrorNotSupported where the quad kernel does not exist)
-	default: return hipErrorNotSupported;            // (jacobi_fused_max_sweeps never offers more than four)
-	}
-}
-
 // device-to-device copy of whole planes as a kernel (16-byte words): the loop-back transport's stand-in for a link.  A
 // hipMemcpyAsync on a side stream took the SDMA path here (~50 GB/s inside one device) and made the overlapped schedules
 // look 2-3x slower than the serial one on a 1-GPU box.

@@ -121,5 +121,4 @@ def test_the_shipped_library_offers_ten_switches():
     assert capi.load().fx_set_knob(b"STRIP4_OCTET", b"0") == capi.FX_E_INVALID
     import subprocess
     syms = subprocess.run(["nm", "-D", "--defined-only", build.LIB], capture_output=True, text=True, check=True).stdout
-    assert "k_jacobi_strip4o" in syms or True                        # (kernels are device symbols; the host stubs carry their names)
     assert "k_jacobi_strip4q" not in syms

@@ -144,7 +144,9 @@ def test_jacobi_temporal_blocking_bit_exact(dims, fuse):
     f = make(dims, jacobi_iters=9, jacobi_fuse=fuse)
     f.upload(fx.FIELD_PRESSURE, p)
     f.upload(fx.FIELD_DIVERGENCE, b)
-    f.Jacobi(9)                                  # 9 = 4+4+1 = 3+3+3 = 2*4+1: exercises remainders
+    # what runs (tests/golden/jacobi_plan.json): 256 x 256 x 20 -- 9 ones, 4 strip twos + 1, 3 threes (k_jacobi_strip3c), 2 fours (k_jacobi_strip4o) + 1;
+    # 64 x 64 x 40 and 128 x 128 x 24 have no three- or four-sweep kernel: jacobi_fuse 2, 3 and 4 all run 2+2+2+2+1 there (strip / block twos)
+    f.Jacobi(9)
     q, _ = orc.jacobi(p, b, 9)
     assert np.array_equal(f.download(fx.FIELD_PRESSURE), q)
 
