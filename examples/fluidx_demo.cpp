@@ -2,7 +2,7 @@
 // OnUpdate's time-step rule (:266) and default camera (:243-253), PopulateCommandList's Simulate + Render
 // (:465,489-490), minus the window.  Build (after `python -m fluidx12_amd.build`):
 //   hipcc -std=c++17 examples/fluidx_demo.cpp -o fluidx_demo -Lfluidx12_amd -lfluidx_hip -Wl,-rpath,$PWD/fluidx12_amd
-// Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck]
+// Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
 #include <chrono>
@@ -91,6 +91,7 @@ int main(int argc, char** argv)
 	const char* radiance = nullptr;                     // FluidGI.bat: -radiance Assets/rnl_cross.dds
 	const char* resume = nullptr;                       // not in the reference: continue from / leave behind a state file
 	const char* checkpoint = nullptr;
+	float vorticity = 0.0f;                             // not in the reference: strength of the vorticity confinement, 0 = off
 	for (int i = 1; i < argc; ++i) {
 		if (!std::strcmp(argv[i], "-gridSize") && i + 3 < argc) { grid.x = atoi(argv[++i]); grid.y = atoi(argv[++i]); grid.z = atoi(argv[++i]); }
 		else if (!std::strcmp(argv[i], "-maxRaySamples") && i + 1 < argc) maxRay = atoi(argv[++i]);
@@ -100,6 +101,7 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-radiance") && i + 1 < argc) radiance = argv[++i];
 		else if (!std::strcmp(argv[i], "-resume") && i + 1 < argc) resume = argv[++i];
 		else if (!std::strcmp(argv[i], "-checkpoint") && i + 1 < argc) checkpoint = argv[++i];
+		else if (!std::strcmp(argv[i], "-vorticity") && i + 1 < argc) vorticity = (float)atof(argv[++i]);
 	}
 	Fluid fluid;
 	if (!fluid.Init(nullptr, width, height, grid)) {   // ThrowIfFailed(E_FAIL) in the reference (FluidX12.cpp:198-200)
@@ -107,6 +109,7 @@ int main(int argc, char** argv)
 		return 1;
 	}
 	fluid.SetMaxSamples(maxRay, maxLight);
+	if (vorticity != 0.0f && !fluid.SetVorticityConfinement(vorticity)) { std::fprintf(stderr, "-vorticity %g: %s\n", vorticity, fx_error_string(fluid.LastStatus())); return 1; }
 	if (resume && !fluid.LoadCheckpoint(resume)) { std::fprintf(stderr, "cannot resume from %s: %s\n", resume, fx_error_string(fluid.LastStatus())); return 1; }
 	LightProbe probe;                                   // FluidX12.cpp:189-195, 205-210: load, TransformSH, SetSH
 	if (radiance) {

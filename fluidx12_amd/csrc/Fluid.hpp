@@ -95,6 +95,9 @@ public:
 		return m_status == FX_OK;
 	}
 
+	// not in the reference: vorticity confinement between advection and divergence (fx_set_vorticity_confinement); 0 = off (default)
+	bool SetVorticityConfinement(float epsilon) { m_status = fx_set_vorticity_confinement(m_ctx, epsilon); return m_status == FX_OK; }
+
 	// not in the reference (its state dies with the window): whole-grid state files, see fx_checkpoint_save
 	bool SaveCheckpoint(const char* path) { m_status = fx_checkpoint_save(m_ctx, path); return m_status == FX_OK; }
 	bool LoadCheckpoint(const char* path) { m_status = fx_checkpoint_load(m_ctx, path); return m_status == FX_OK; }

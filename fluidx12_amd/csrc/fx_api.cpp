@@ -374,6 +374,22 @@ int fx_advect(fx_ctx* ctx, void* stream)
 	return advect_range(ctx, s, owned(ctx), false);
 }
 
+int fx_set_vorticity_confinement(fx_ctx* ctx, float epsilon)
+{
+	if (!ctx || !std::isfinite(epsilon) || epsilon < 0.0f) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // a slab would need two planes of velocity[1] across each face
+	ctx->vort_eps = epsilon;
+	return FX_OK;
+}
+
+int fx_confine_vorticity(fx_ctx* ctx, void* stream)
+{
+	if (!ctx || ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	return confine_phase(ctx, pick_stream(ctx, stream));
+}
+
 int fx_divergence(fx_ctx* ctx, void* stream)
 {
 	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;

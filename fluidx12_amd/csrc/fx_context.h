@@ -18,7 +18,7 @@ struct fx_ctx {
 	bool owns_stream;
 
 	// ---- fields (XUSG textures of Fluid.h:93-97 -> hipMalloc) --------------------------------
-	void* vel[2];                   // 3 component planes each, local extent incl. halo
+	void* vel[2];                   // 3 component planes each, local extent incl. halo ([0] / [1] are roles: the confinement pass swaps the pointers, fx_schedule.cpp confine_phase)
 	void* col[2];                   // rgba texels
 	float* p[2];                    // pressure ping-pong (m_incompress); p[p_cur] is current
 	int p_cur;
@@ -58,6 +58,8 @@ struct fx_ctx {
 	const float* depth;             // float[viewport_h][viewport_w] the depth variants read: the caller's device buffer or depth_own; null = detached
 	float* depth_own;               // the context's copy of a host depth buffer (lazily allocated)
 	float depth_zn, depth_zf;
+	// vorticity confinement (fx_set_vorticity_confinement; configuration like the scene depth: kept across fx_update_frame, never checkpointed or digested)
+	float vort_eps = 0.0f;          // 0 = off
 	float wvp[16];                  // CBPerObject.WorldViewProj (Fluid.cpp:315-318) as its four constant-buffer rows, set by fx_update_frame
 	float* env;                     // radiance cube of the sky pass, float [6][env_n][env_n][3] (fx_set_environment)
 	uint32_t env_n;

@@ -69,6 +69,9 @@ hipError_t launch_advect_lds(const Geom& g, const SimParams& sp, int half_store,
 // far_scratch: advect_far_words(g, planes) words lent by the caller (its first two words ZEROED once; far_parity alternates over the launches that report *far_used) let the staged kernel
 // defer far-tracing voxels to a second, small launch
 size_t advect_far_words(const Geom& g, int nzp);
+// vorticity confinement of a whole-grid velocity (fx_vorticity.hip), vel_in -> vel_out (never in place: the cell stencil has radius 2);
+// hipErrorNotSupported for a slab geometry
+hipError_t launch_confine_vorticity(const Geom& g, int half_store, const void* vel_in, void* vel_out, float eps, float dt, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
 // one lock-step sweep p_in -> p_out on planes [z_begin, z_end); frozen may be null
 hipError_t launch_jacobi_sweep(const Geom& g, const float* p_in, const float* b, float* p_out, uint8_t* frozen,

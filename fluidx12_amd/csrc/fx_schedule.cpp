@@ -281,6 +281,22 @@ int advect_all(fx_ctx* ctx, std::vector<fx_ctx*>& M, hipStream_t s)
 	return FX_OK;
 }
 
+// Vorticity confinement (fx_vorticity.hip) finishes the advected velocity, so its time is booked with the advection.  The pass cannot run
+// in place; velocity[0] is dead between the advection and the projection of a single domain, so the result goes there and the two
+// pointers swap: velocity[1] then names the confined field, the projection overwrites the other buffer as always.  Everybody who holds
+// these pointers reads them per call (fx_upload / fx_download / fx_field_digest and through them the checkpoint, the exchange items and
+// launch_face_need of slab ranks -- which never get here, fx_set_vorticity_confinement refuses them -- and the dt = 0 copy, which the
+// pass does not precede: it is a no-op then).
+int confine_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!(ctx->vort_eps > 0.0f) || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	FX_HIP(launch_confine_vorticity(ctx->g, ctx->half, ctx->vel[1], ctx->vel[0], ctx->vort_eps, ctx->time_step, s));
+	std::swap(ctx->vel[0], ctx->vel[1]);
+	return FX_OK;
+}
+
 int divergence_phase(fx_ctx* ctx, hipStream_t s)
 {
 	DeviceGuard dg(ctx->device);
@@ -683,6 +699,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		for (fx_ctx* m : M) m->col_halo_buf = (int)m->frame_parity;
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
+		for (fx_ctx* m : M) if ((rc = confine_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with epsilon > 0 only)
 		const ExchSpec uz{ EX_UZ1, 1, 0 };
 		if ((rc = do_exchange(ctx, M, &uz, 1, ON_COMPUTE, s))) return rc;
 		if (takes_sparse_solver(ctx, ctx->desc.jacobi_iters) && jacobi_freeze_can_fuse_divergence(ctx->g)) ctx->fz_fuse_div = true;   // k_freeze_dense computes it

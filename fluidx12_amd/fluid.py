@@ -225,6 +225,17 @@ class Fluid:
     def Advect(self, stream=None):
         capi.check(self._lib.fx_advect(self._ctx, stream), "Advect")
 
+    def SetVorticityConfinement(self, eps):
+        """strength of the vorticity confinement pass between advection and divergence (fx_set_vorticity_confinement); 0 = off (default).
+        Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid contexts only."""
+        self._need()
+        capi.check(self._lib.fx_set_vorticity_confinement(self._ctx, float(eps)), "SetVorticityConfinement")
+
+    def ConfineVorticity(self, stream=None):
+        """the confinement stage alone, on VELOCITY1 (fx_confine_vorticity); VELOCITY is unspecified afterwards until the next Project"""
+        self._need()
+        capi.check(self._lib.fx_confine_vorticity(self._ctx, stream), "ConfineVorticity")
+
     def Divergence(self, stream=None):
         capi.check(self._lib.fx_divergence(self._ctx, stream), "Divergence")
 

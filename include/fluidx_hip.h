@@ -240,6 +240,27 @@ int fx_divergence(fx_ctx* ctx, void* stream);
 int fx_jacobi(fx_ctx* ctx, void* stream, uint32_t iters);
 int fx_project(fx_ctx* ctx, void* stream);
 
+/* Vorticity confinement (Fedkiw, Stam, Jensen 2001; no reference counterpart -- the reference's only swirl is the fixed term inside its
+ * impulse, CSAdvect.hlsl:63-65).  The semi-Lagrangian step wears the small eddies down; with epsilon > 0 fx_simulate runs one more pass
+ * between the advection and the divergence, on the advected velocity u = VELOCITY1, in index space like the divergence and the projection
+ * (unit cell spacing, neighbour indices clamped to the grid; D = half the difference of the two clamped neighbours):
+ *   w = curl u      m = |w|      g = grad m      u' = u + (g x w) * (epsilon * dt) / (|g| + 1e-6)
+ * fp32, every operation rounded on its own (tests/vorticity_ref.py restates it in numpy, bit for bit); fp16 storage widens on load and rounds
+ * u' once (RNE).  2-D grids: w = (0, 0, wz), uz is left alone.  epsilon multiplies N x w per cell: on a cubic grid Fedkiw's eps * h * (N x w);
+ * non-cubic grids are treated in index space like the divergence.  The pass is explicit: keeping epsilon * dt small enough for the flow at
+ * hand is the caller's business.
+ * fx_set_vorticity_confinement: 0 = off (default): every call behaves exactly as without this function.  Configuration like the scene depth:
+ * kept across fx_update_frame, not checkpointed (set it again after fx_checkpoint_load), not part of fx_field_digest.  FX_E_INVALID for a
+ * negative or non-finite epsilon and for a context that owns fewer planes than the grid (slab ranks, over RCCL or in-process groups, are
+ * out of scope: the pass would need two planes of all three VELOCITY1 components across each face); FX_E_STATE for FX_FLAG_RENDER_ONLY.
+ * fx_confine_vorticity: the stage alone, beside fx_advect / fx_divergence / fx_jacobi / fx_project (parity tests, micro-benchmarks), with
+ * the context's epsilon and the time step of the last fx_update_frame; nothing (FX_OK) while either is 0.  The pass cannot run in place:
+ * it writes the buffer behind FX_FIELD_VELOCITY and the two names swap, so afterwards FX_FIELD_VELOCITY1 is the confined field and
+ * FX_FIELD_VELOCITY is unspecified until the next fx_project (or fx_simulate) has written it.
+ * Timing: the pass finishes the advected velocity, its time is booked into fx_timing.advect_ms. */
+int fx_set_vorticity_confinement(fx_ctx* ctx, float epsilon);
+int fx_confine_vorticity(fx_ctx* ctx, void* stream);
+
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
 int fx_sh_transform(fx_ctx* ctx, const float* cube, uint32_t n, float* out27);
