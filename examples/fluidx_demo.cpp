@@ -3,6 +3,7 @@
 // (:465,489-490), minus the window.  Build (after `python -m fluidx12_amd.build`):
 //   hipcc -std=c++17 examples/fluidx_demo.cpp -o fluidx_demo -Lfluidx12_amd -lfluidx_hip -Wl,-rpath,$PWD/fluidx12_amd
 // Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
+//        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
 #include <chrono>
@@ -92,6 +93,8 @@ int main(int argc, char** argv)
 	const char* resume = nullptr;                       // not in the reference: continue from / leave behind a state file
 	const char* checkpoint = nullptr;
 	float vorticity = 0.0f;                             // not in the reference: strength of the vorticity confinement, 0 = off
+	bool lightSet = false, pointLight = false, colorSet = false, ambientSet = false;   // not in the reference: its light is three constants (Fluid.cpp:169-173)
+	float lightPos[3] = { 75.0f, 75.0f, -75.0f }, lightColor[4] = {}, ambient[4] = {};
 	for (int i = 1; i < argc; ++i) {
 		if (!std::strcmp(argv[i], "-gridSize") && i + 3 < argc) { grid.x = atoi(argv[++i]); grid.y = atoi(argv[++i]); grid.z = atoi(argv[++i]); }
 		else if (!std::strcmp(argv[i], "-maxRaySamples") && i + 1 < argc) maxRay = atoi(argv[++i]);
@@ -102,6 +105,10 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-resume") && i + 1 < argc) resume = argv[++i];
 		else if (!std::strcmp(argv[i], "-checkpoint") && i + 1 < argc) checkpoint = argv[++i];
 		else if (!std::strcmp(argv[i], "-vorticity") && i + 1 < argc) vorticity = (float)atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "-light") && i + 3 < argc) { for (float& v : lightPos) v = (float)atof(argv[++i]); lightSet = true; }
+		else if (!std::strcmp(argv[i], "-pointLight")) { pointLight = true; lightSet = true; }
+		else if (!std::strcmp(argv[i], "-lightColor") && i + 4 < argc) { for (float& v : lightColor) v = (float)atof(argv[++i]); colorSet = lightSet = true; }
+		else if (!std::strcmp(argv[i], "-ambient") && i + 4 < argc) { for (float& v : ambient) v = (float)atof(argv[++i]); ambientSet = lightSet = true; }
 	}
 	Fluid fluid;
 	if (!fluid.Init(nullptr, width, height, grid)) {   // ThrowIfFailed(E_FAIL) in the reference (FluidX12.cpp:198-200)
@@ -110,6 +117,11 @@ int main(int argc, char** argv)
 	}
 	fluid.SetMaxSamples(maxRay, maxLight);
 	if (vorticity != 0.0f && !fluid.SetVorticityConfinement(vorticity)) { std::fprintf(stderr, "-vorticity %g: %s\n", vorticity, fx_error_string(fluid.LastStatus())); return 1; }
+	if (lightSet && grid.z <= 1) std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: a 2-D grid has no light; ignored\n");
+	if (lightSet && grid.z > 1 && !fluid.SetLight(lightPos, pointLight, colorSet ? lightColor : nullptr, ambientSet ? ambient : nullptr)) {
+		std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: %s\n", fx_error_string(fluid.LastStatus()));
+		return 1;
+	}
 	if (resume && !fluid.LoadCheckpoint(resume)) { std::fprintf(stderr, "cannot resume from %s: %s\n", resume, fx_error_string(fluid.LastStatus())); return 1; }
 	LightProbe probe;                                   // FluidX12.cpp:189-195, 205-210: load, TransformSH, SetSH
 	if (radiance) {

@@ -22,6 +22,7 @@ ABI_VERSION = 7                      # FX_ABI_VERSION of include/fluidx_hip.h
 (FIELD_VELOCITY, FIELD_VELOCITY1, FIELD_COLOR, FIELD_COLOR_PREV, FIELD_PRESSURE, FIELD_DIVERGENCE,
  FIELD_LIGHTMAP, FIELD_CUBEMAP, FIELD_TARGET, FIELD_TARGET_FLOAT, FIELD_CUBE_DEPTH) = range(11)
 DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is device memory, read in place
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 
 
 class Desc(C.Structure):
@@ -36,6 +37,11 @@ class FrameInfo(C.Structure):
     _fields_ = [("cube_lod", C.c_uint32), ("cube_size", C.c_uint32), ("ray_samples", C.c_uint32),
                 ("visibility_mask", C.c_uint32), ("frame_parity", C.c_uint32), ("edge_pixels", C.c_float),
                 ("time_step", C.c_float), ("world_view_proj_i", C.c_float * 16), ("screen_to_world", C.c_float * 16)]
+
+
+class Light(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("position", C.c_float * 3), ("color", C.c_float * 4),
+                ("ambient", C.c_float * 4)]
 
 
 class Timing(C.Structure):
@@ -83,6 +89,8 @@ SYMBOLS = {
     "fx_clear_render_target": (C.c_int, [_vp, _vp, _fp]),
     "fx_render_cube": (C.c_int, [_vp, _vp, C.c_uint8]),
     "fx_set_scene_depth": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32]),
+    "fx_set_light": (C.c_int, [_vp, C.POINTER(Light)]),
+    "fx_get_light": (C.c_int, [_vp, C.POINTER(Light)]),
     "fx_dds_cube_info": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fx_dds_decode_cube": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _fp, C.c_size_t]),
     "fx_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -95,6 +95,21 @@ public:
 		return m_status == FX_OK;
 	}
 
+	// not in the reference (its light is three constants, Fluid.cpp:169-173): the scene light of the following renders (fx_set_light).
+	// position: world space of UpdateFrame's view matrix (the volume is [-10, 10]^3 there); point = false: only its direction matters,
+	// true: the light's place -- shadow rays run to it and end there.  color / ambient: rgb x intensity (w).  nullptr: the reference's constants
+	bool SetLight(const fx_light* light) { m_status = fx_set_light(m_ctx, light); return m_status == FX_OK; }
+	bool SetLight(const float position[3], bool point, const float color[4] = nullptr, const float ambient[4] = nullptr)
+	{
+		fx_light l;
+		if ((m_status = fx_get_light(m_ctx, &l)) != FX_OK) return false;
+		l.kind = point ? FX_LIGHT_POINT : FX_LIGHT_DIRECTIONAL;
+		for (int a = 0; a < 3; ++a) l.position[a] = position[a];
+		for (int a = 0; a < 4; ++a) { if (color) l.color[a] = color[a]; if (ambient) l.ambient[a] = ambient[a]; }
+		return SetLight(&l);
+	}
+	bool GetLight(fx_light* out) { m_status = fx_get_light(m_ctx, out); return m_status == FX_OK; }
+
 	// not in the reference: vorticity confinement between advection and divergence (fx_set_vorticity_confinement); 0 = off (default)
 	bool SetVorticityConfinement(float epsilon) { m_status = fx_set_vorticity_confinement(m_ctx, epsilon); return m_status == FX_OK; }
 

@@ -60,12 +60,7 @@ int fx_update_frame(fx_ctx* ctx, float time_step, uint8_t frame_index,
 			for (int r = 0; r < 4; ++r)
 				for (int q = 0; q < 4; ++q) { c->fc.wvp_i[r * 4 + q] = wvpI.m[q][r]; c->wvp[r * 4 + q] = wvp.m[q][r]; }   // (the forward one: scene depth)
 			for (int a = 0; a < 3; ++a) c->fc.eye_pt[a] = eye[a];
-			const float pi = 3.141592654f;
-			const float lp[3] = { 75.0f, 75.0f, -75.0f };                        // Fluid.cpp:169-173
-			const float lc[4] = { 1.0f, 0.7f, 0.3f, pi * 3.0f }, am[4] = { 1.0f, 1.0f, 1.0f, pi * 1.5f };
-			std::memcpy(c->fc.light_pt, lp, sizeof lp);
-			std::memcpy(c->fc.light_color, lc, sizeof lc);
-			std::memcpy(c->fc.ambient, am, sizeof am);
+			// (light point, light colour and ambient -- Fluid.cpp:169-173 -- belong to the context: fx_create, fx_set_light)
 
 			// EstimateCubeMapLOD (Fluid.cpp:141-166)
 			static const Vec3 corners[8] = { {1,1,1},{-1,1,1},{1,-1,1},{-1,-1,1},{-1,1,-1},{1,1,-1},{-1,-1,-1},{1,-1,-1} };
@@ -153,6 +148,7 @@ struct Marches {
 		dep = depth_args(ctx, ctx->cube_lod, &da) ? &da : nullptr;
 	}
 	const float* sh() const { return c->has_sh ? c->sh_dev : nullptr; }
+	int point() const { return c->light_kind == FX_LIGHT_POINT ? 1 : 0; }     // which instantiation of the light-ray kernels (fx_set_light)
 	hipError_t build(bool for_light = false)
 	{
 		if (!accel || built) return hipSuccess;
@@ -182,9 +178,9 @@ struct Marches {
 	{
 		hipError_t e = build(true);
 		if (e != hipSuccess) return e;
-		if (accel) return launch_accel_light(c->g, c->accel, c->lightmap, c->fc, sh(), c->max_light_samples, s, cnt, filled);
+		if (accel) return launch_accel_light(c->g, c->accel, c->lightmap, c->fc, sh(), c->max_light_samples, s, cnt, filled, point());
 		c->lightmap_filled = false;
-		return launch_raymarch_light(c->g, c->half, color, c->lightmap, c->fc, sh(), c->max_light_samples, s, cnt);
+		return launch_raymarch_light(c->g, c->half, color, c->lightmap, c->fc, sh(), c->max_light_samples, s, cnt, point());
 	}
 	hipError_t view(int size, uint8_t* cube, bool separate)   // Fluid.cpp:880-908 (separate) / :825-855 (merged)
 	{
@@ -192,9 +188,9 @@ struct Marches {
 		if (e != hipSuccess) return e;
 		const uint32_t ns = c->ray_samples;
 		if (accel) return launch_accel_view(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), size,
-			c->visibility_mask, ns, c->max_light_samples, separate, cube, c->accel, s, cnt, dep);
+			c->visibility_mask, ns, c->max_light_samples, separate, cube, c->accel, s, cnt, dep, point());
 		return launch_raymarch_view(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), size,
-			c->visibility_mask, ns, c->max_light_samples, separate, cube, s, cnt, dep);
+			c->visibility_mask, ns, c->max_light_samples, separate, cube, s, cnt, dep, point());
 	}
 	hipError_t direct(int W, int H, bool separate)      // rayCastVDirect Fluid.cpp:953-972 / rayCastDirect :932-951
 	{
@@ -202,9 +198,9 @@ struct Marches {
 		if (e != hipSuccess) return e;
 		const uint32_t ns = separate ? c->ray_samples : c->max_ray_samples;
 		if (accel) return launch_accel_direct(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), W, H,
-			ns, c->max_light_samples, separate, c->target, c->target_float, c->accel, s, cnt, dep);
+			ns, c->max_light_samples, separate, c->target, c->target_float, c->accel, s, cnt, dep, point());
 		return launch_raycast_direct(c->g, c->half, color, separate ? c->lightmap : nullptr, c->fc, separate ? nullptr : sh(), W, H,
-			ns, c->max_light_samples, separate, c->target, c->target_float, s, cnt, dep);
+			ns, c->max_light_samples, separate, c->target, c->target_float, s, cnt, dep, point());
 	}
 };
 
@@ -316,6 +312,35 @@ int fx_set_scene_depth(fx_ctx* ctx, void* stream, const float* depth, uint32_t w
 	}
 	ctx->depth_zn = z_near;
 	ctx->depth_zf = z_far;
+	return FX_OK;
+}
+
+int fx_set_light(fx_ctx* ctx, const fx_light* light)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->g.Zg <= 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;       // 2-D grids have no light; a slab of a group does not march rays
+	if (!light) { default_light(ctx); return FX_OK; }
+	if (light->struct_size != sizeof(fx_light)) return FX_E_INVALID;
+	if (light->kind != FX_LIGHT_DIRECTIONAL && light->kind != FX_LIGHT_POINT) return FX_E_INVALID;
+	for (int a = 0; a < 3; ++a) if (!std::isfinite(light->position[a])) return FX_E_INVALID;
+	for (int a = 0; a < 4; ++a)                                              // (the light map is unsigned: R11G11B10_FLOAT)
+		if (!std::isfinite(light->color[a]) || !std::isfinite(light->ambient[a]) || light->color[a] < 0.0f || light->ambient[a] < 0.0f) return FX_E_INVALID;
+	if (light->kind == FX_LIGHT_DIRECTIONAL && light->position[0] == 0.0f && light->position[1] == 0.0f && light->position[2] == 0.0f) return FX_E_INVALID;
+	std::memcpy(ctx->fc.light_pt, light->position, sizeof ctx->fc.light_pt);
+	std::memcpy(ctx->fc.light_color, light->color, sizeof ctx->fc.light_color);
+	std::memcpy(ctx->fc.ambient, light->ambient, sizeof ctx->fc.ambient);
+	ctx->light_kind = light->kind;
+	return FX_OK;
+}
+
+int fx_get_light(fx_ctx* ctx, fx_light* out)
+{
+	if (!ctx || !out) return FX_E_INVALID;
+	out->struct_size = sizeof(fx_light);
+	out->kind = ctx->light_kind;
+	std::memcpy(out->position, ctx->fc.light_pt, sizeof out->position);
+	std::memcpy(out->color, ctx->fc.light_color, sizeof out->color);
+	std::memcpy(out->ambient, ctx->fc.ambient, sizeof out->ambient);
 	return FX_OK;
 }
 

@@ -138,6 +138,7 @@ int fx_create(fx_ctx** out, const fx_desc* d)
 	if (!ctx) return FX_E_NOMEM;
 	ctx->desc = *d;
 	ctx->desc.slab_z0 = z0; ctx->desc.slab_nz = nz;
+	default_light(ctx);
 	if (!ctx->desc.halo_advect) ctx->desc.halo_advect = kDefaultAdvectHalo;
 	if (!ctx->desc.halo_jacobi) ctx->desc.halo_jacobi = kDefaultJacobiHalo;
 	if (!slab) { ctx->desc.halo_advect = 0; }

@@ -25,6 +25,16 @@ const uint32_t kDefaultJacobiHalo = 8;   // sweeps per pressure exchange: 5 mess
 
 inline hipStream_t pick_stream(fx_ctx* ctx, void* s) { return s ? (hipStream_t)s : ctx->stream; }
 inline size_t elem_size(const fx_ctx* c) { return c->half ? 2 : 4; }
+// the reference's light (Fluid.cpp:169-173): what a context starts with and fx_set_light(ctx, NULL) returns to
+inline void default_light(fx_ctx* c)
+{
+	const float pi = 3.141592654f;
+	const float lp[3] = { 75.0f, 75.0f, -75.0f };
+	const float lc[4] = { 1.0f, 0.7f, 0.3f, pi * 3.0f }, am[4] = { 1.0f, 1.0f, 1.0f, pi * 1.5f };
+	for (int a = 0; a < 3; ++a) c->fc.light_pt[a] = lp[a];
+	for (int a = 0; a < 4; ++a) { c->fc.light_color[a] = lc[a]; c->fc.ambient[a] = am[a]; }
+	c->light_kind = FX_LIGHT_DIRECTIONAL;
+}
 
 struct DeviceGuard {
 	int prev = -1;

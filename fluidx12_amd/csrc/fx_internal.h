@@ -175,14 +175,15 @@ hipError_t launch_from_storage(const void* src, float* dst, size_t n, int half_s
 const int kSampleShards = 64;
 // plain path (fx_render.hip): every sample gathers its taps
 hipError_t launch_raymarch_light(const Geom& g, int half_store, const void* color, uint32_t* lightmap,
-	const FrameConsts& fc, const float* sh, uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr);
+	const FrameConsts& fc, const float* sh, uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr, int point_light = 0);
+// (point_light, here and below: the FX_LIGHT_POINT instantiations of the kernels that cast light rays -- fx_march.h point_light_ray)
 hipError_t launch_raymarch_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int cube_size, uint32_t mask, uint32_t num_samples,
-	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
+	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr, int point_light = 0);
 // direct screen-space march (row f-2): one ray per pixel, blended into the RGBA8 target (and/or kept as float4)
 hipError_t launch_raycast_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate,
-	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
+	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr, int point_light = 0);
 // accelerated path (fx_render_accel.hip; the default, bit-identical to the plain one).  Device scratch, owned by the context:
 struct RenderAccel {
 	float* occ;          // per 4^3 block: max alpha over everything a sample based in the block can touch (n cells) + the maxima it is dilated from (n cells)
@@ -211,13 +212,13 @@ struct LightFill { uint32_t* lightmap; const FrameConsts* fc; int has_sh; bool i
 hipError_t launch_accel_build(const Geom& g, int half_store, const void* color, const RenderAccel& a, hipStream_t s, bool alpha_current = false,
 	const LightFill* fill = nullptr, bool* filled = nullptr);
 hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lightmap, const FrameConsts& fc, const float* sh,
-	uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr, bool filled = false);
+	uint32_t num_samples, hipStream_t s, unsigned long long* counters = nullptr, bool filled = false, int point_light = 0);
 hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int cube_size, uint32_t mask, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* cube, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
+	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr, int point_light = 0);
 hipError_t launch_accel_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* target, float* out_float, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr);
+	unsigned long long* counters = nullptr, const DepthArgs* depth = nullptr, int point_light = 0);
 // 2-D visualiser (PSVisualizeColor): colour[parity] of a Z = 1 grid onto the render target
 hipError_t launch_visualize_color(const Geom& g, int half_store, const void* color, int W, int H, uint8_t* target, float* out_float, hipStream_t s);
 hipError_t launch_lightmap_decode(const uint32_t* lightmap, float* out, size_t n, hipStream_t s);

@@ -300,10 +300,11 @@ __device__ __forceinline__ bool light_step(float density, float stepScale, float
 }
 
 // CastLightRay (RayMarch.hlsli:215-247); ns = density samples taken (FX_OPT_COUNT_SAMPLES; a dead register otherwise);
-// K = samples fetched per round trip (see the head of the file)
-template <int K, class V>
+// K = samples fetched per round trip (see the head of the file).  POINT (the ray to a point light, fx_set_light): a sample is taken
+// only while t < tEnd, the distance to the light -- the ray ends at the light (the reference's compiled-out variant marches on)
+template <int K, bool POINT = false, class V>
 __device__ void cast_light_ray(float& transm, const Geom& g, const V& vol,
-	float ox, float oy, float oz, float dx, float dy, float dz, float stepScale, uint32_t numSamples, uint32_t& ns)
+	float ox, float oy, float oz, float dx, float dy, float dz, float stepScale, uint32_t numSamples, uint32_t& ns, float tEnd = 0.0f)
 {
 	float t = stepScale, prev = 0.0f;
 	uint32_t i = 0;
@@ -314,6 +315,7 @@ __device__ void cast_light_ray(float& transm, const Geom& g, const V& vol,
 		bool gather = false;
 		while (true) {
 			if (i >= numSamples) { live = false; break; }
+			if (POINT && !(t < tEnd)) { live = false; break; }
 			const float px = fmaf(dx, t, ox), py = fmaf(dy, t, oy), pz = fmaf(dz, t, oz);
 			if (outside(px, py, pz)) { live = false; break; }
 			++ns;
@@ -340,7 +342,7 @@ __device__ void cast_light_ray(float& transm, const Geom& g, const V& vol,
 						tk = fmaf(stepScale, 1.0f, tk);
 						++ik;
 						const float px = fmaf(dx, tk, ox), py = fmaf(dy, tk, oy), pz = fmaf(dz, tk, oz);
-						if (ik >= numSamples || outside(px, py, pz)) chain = false;
+						if (ik >= numSamples || (POINT && !(tk < tEnd)) || outside(px, py, pz)) chain = false;
 						else {
 							const Base b = make_base(g, fmaf(px, 0.5f, 0.5f), fmaf(py, 0.5f, 0.5f), fmaf(pz, 0.5f, 0.5f));
 							if (vol.dense(b)) { kind[k] = 2; tp[k] = make_taps(g, b); } else kind[k] = 1;
@@ -431,6 +433,32 @@ __device__ __forceinline__ void light_dir_local(const FrameConsts& fc, float& lx
 	lx *= r; ly *= r; lz *= r;
 }
 
+// ---- point light (the reference's _POINT_LIGHT_ variants; fx_set_light FX_LIGHT_POINT) ----------------------------------------
+// localSpaceLightPt = mul(float4(g_lightPt, 1), g_worldI) (CSRayMarchL.hlsl:49, CSRayMarch.hlsl:134, PSRayCast.hlsl:64): the chain of the eye point
+__device__ __forceinline__ void light_point_local(const FrameConsts& fc, float& lx, float& ly, float& lz)
+{
+	float p[3];
+#pragma unroll
+	for (int a = 0; a < 3; ++a) {
+		const float* r = fc.world_i + 4 * a;
+		p[a] = fmaf(r[3], 1.0f, fmaf(fc.light_pt[2], r[2], fmaf(fc.light_pt[1], r[1], fc.light_pt[0] * r[0])));
+	}
+	lx = p[0]; ly = p[1]; lz = p[2];
+}
+
+// the ray from (ox, oy, oz) to the light point: normalize(localSpaceLightPt - origin) (CSRayMarchL.hlsl:50, CSRayMarch.hlsl:165,
+// PSRayCast.hlsl:95) and the distance at which it ends.  A light vector of length zero (the light sits on the origin) or not finite casts
+// no ray: direction 0 and end 0, so that no sample is taken, the transmittance stays 1 and no NaN reaches an address
+__device__ __forceinline__ void point_light_ray(float px, float py, float pz, float ox, float oy, float oz, float& dx, float& dy, float& dz, float& tEnd)
+{
+	const float vx = px - ox, vy = py - oy, vz = pz - oz;
+	const float l2 = dot3(vx, vy, vz, vx, vy, vz);
+	const bool ok = l2 > 0.0f && l2 <= 3.40282347e+38f;
+	const float r = rsqf(l2);
+	dx = ok ? vx * r : 0.0f; dy = ok ? vy * r : 0.0f; dz = ok ? vz * r : 0.0f;
+	tEnd = ok ? sqrtf(l2) : 0.0f;
+}
+
 // the light-map value of one voxel (CSRayMarchL.hlsl:22-79) given its centre sample; `lit` = density >= 0.01 (:44)
 __device__ __forceinline__ uint32_t light_value(const FrameConsts& fc, bool has_sh, float shadow, float ao, const float irr[3])
 {
@@ -486,7 +514,8 @@ __device__ __forceinline__ uint32_t to_unorm8(float v)
 // the march of one view ray (CSRayMarch.hlsl:140-190 == PSRayCast.hlsl:72-122): o = origin on/in the cube, d = unit
 // direction, tMax = ray parameter at the cube-map target (the direct pixel march has none: FLT_MAX).  `go` = this lane has a ray.
 // K = samples fetched per round trip (the merged march, whose samples cast rays of their own, takes one).
-template <class V, bool SEPARATE, int K>
+// POINT (merged march only): each visible sample's nested light ray runs to the light point and ends there (point_light_ray)
+template <class V, bool SEPARATE, int K, bool POINT = false>
 __device__ __forceinline__ void march_ray(const Geom& g, const V& vol, const uint32_t* __restrict__ lightmap, const FrameConsts& fc,
 	const float* __restrict__ sh, const float o[3], const float d[3], float tMax, uint32_t numSamples, uint32_t numLightSamples, bool go,
 	float& sr, float& sg, float& sb, float& sa, uint32_t& nv, uint32_t& nl, uint32_t& nm)
@@ -495,7 +524,7 @@ __device__ __forceinline__ void march_ray(const Geom& g, const V& vol, const uin
 	const float stepScale = 3.46410155f / (float)numSamples;
 	const float lightStep = 3.46410155f / (float)numLightSamples;
 	float lx = 0.0f, ly = 0.0f, lz = 0.0f;
-	if (!SEPARATE) light_dir_local(fc, lx, ly, lz);
+	if (!SEPARATE) { if (POINT) light_point_local(fc, lx, ly, lz); else light_dir_local(fc, lx, ly, lz); }
 
 	sr = 0.0f; sg = 0.0f; sb = 0.0f; sa = 0.0f;
 	float t = 0.0f, prev = 0.0f;
@@ -573,6 +602,11 @@ __device__ __forceinline__ void march_ray(const Geom& g, const V& vol, const uin
 								light[0] = l.x; light[1] = l.y; light[2] = l.z;
 							} else {                                               // RayMarch.hlsli:260-294
 								float shadow = 1.0f, ao = 1.0f, irr[3] = { 0.0f, 0.0f, 0.0f };
+								if (POINT) {
+									float ex, ey, ez, tEnd;
+									point_light_ray(lx, ly, lz, qx, qy, qz, ex, ey, ez, tEnd);
+									cast_light_ray<1, true>(shadow, g, vol, qx, qy, qz, ex, ey, ez, lightStep, numLightSamples, nl, tEnd);
+								} else
 								cast_light_ray<1>(shadow, g, vol, qx, qy, qz, lx, ly, lz, lightStep, numLightSamples, nl);
 								if (sh) gi_term<1>(irr, ao, g, vol, fc, sh, qx, qy, qz, u, v, w, lightStep, numLightSamples, nl);
 #pragma unroll

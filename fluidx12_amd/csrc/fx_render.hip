@@ -10,6 +10,7 @@
 //                        otherwise the merged variant with the nested light march (RayMarch.hlsli:260-294)
 //   k_raycast_direct  <- PSRayCast.hlsl:44-127 / PSRayCastV.hlsl (row f-2)
 // Both view kernels also come as the _HAS_DEPTH_MAP_ variants (a DepthArgs behind the other arguments): the march ends at the scene depth.
+// The kernels that cast light rays also come as the _POINT_LIGHT_ variants (POINT; fx_set_light): the ray runs to the light point and ends there.
 // (paths relative to /root/reference/FluidX12/Content/Shaders/; the march itself lives in fx_march.h).
 // A wave64 = one 8x8 texel tile (view) or 64 consecutive x (light), so the taps of a wave are spatially coherent.
 // Light map = packed R11G11B10_FLOAT like the reference (Fluid.cpp:226), cube map = R8G8B8A8_UNORM.
@@ -18,7 +19,7 @@
 namespace fx {
 
 // ---------------------------------------------------------------------------------------------------
-template <bool HALF>
+template <bool HALF, bool POINT>
 __global__ __launch_bounds__(256) void k_raymarch_light(const Geom g, const typename ColTex<HALF>::T* __restrict__ col,
 	uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh, uint32_t numSamples,
 	unsigned long long* __restrict__ counters)
@@ -38,8 +39,15 @@ __global__ __launch_bounds__(256) void k_raymarch_light(const Geom g, const type
 	if (density >= 0.00999999978f) {                                               // :44
 		const float stepScale = 3.46410155f / (float)numSamples;                   // RayMarch.hlsli:29-30
 		float lx, ly, lz;
+		if (POINT) {                                                               // :49-50
+			float px, py, pz, tEnd;
+			light_point_local(fc, px, py, pz);
+			point_light_ray(px, py, pz, ox, oy, oz, lx, ly, lz, tEnd);
+			cast_light_ray<1, true>(shadow, g, vol, ox, oy, oz, lx, ly, lz, stepScale, numSamples, ns, tEnd);   // :55
+		} else {
 		light_dir_local(fc, lx, ly, lz);
 		cast_light_ray<1>(shadow, g, vol, ox, oy, oz, lx, ly, lz, stepScale, numSamples, ns);   // :55
+		}
 		if (sh) gi_term<1>(irr, ao, g, vol, fc, sh, ox, oy, oz, u, v, w, stepScale, numSamples, ns);   // :59-68
 	}
 	lightmap[((size_t)z * g.Y + y) * g.X + x] = light_value(fc, sh != nullptr, shadow, ao, irr);
@@ -47,7 +55,7 @@ __global__ __launch_bounds__(256) void k_raymarch_light(const Geom g, const type
 }
 
 // Dep: empty, or the scene depth (fx_march.h cube_tmax / direct_tmax)
-template <bool HALF, bool SEPARATE, class... Dep>
+template <bool HALF, bool SEPARATE, bool POINT, class... Dep>
 __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typename ColTex<HALF>::T* __restrict__ col,
 	const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh, int size, uint32_t mask,
 	uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters, const Dep... dep)
@@ -62,7 +70,7 @@ __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typena
 	const PlainVol<HALF> vol{ col };
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
-	march_ray<PlainVol<HALF>, SEPARATE, 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
+	march_ray<PlainVol<HALF>, SEPARATE, 1, POINT>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :192
 	cube[((size_t)face * size + y) * size + x] =
@@ -75,7 +83,7 @@ __global__ __launch_bounds__(64) void k_raymarch_view(const Geom g, const typena
 // taps of a wave stay spatially coherent; output = the shader's premultiplied SV_TARGET, merged into the RGBA8 target
 // with the PREMULTIPLIED blend (Fluid.cpp:670,685) and optionally kept as float4 (parity tests).
 // ---------------------------------------------------------------------------------------------------
-template <bool HALF, bool SEPARATE, class... Dep>
+template <bool HALF, bool SEPARATE, bool POINT, class... Dep>
 __global__ __launch_bounds__(64) void k_raycast_direct(const Geom g, const typename ColTex<HALF>::T* __restrict__ col,
 	const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh, int W, int H,
 	uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ target, float4* __restrict__ out_float,
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(64) void k_raycast_direct(const Geom g, const typen
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
 	const float tMax = direct_tmax(fc, px, py, W, H, o, d, dep...);                // PSRayCast.hlsl:52-56
-	march_ray<PlainVol<HALF>, SEPARATE, 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
+	march_ray<PlainVol<HALF>, SEPARATE, 1, POINT>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, true, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :124
 	if (out_float) out_float[pix] = make_float4(sr, sg, sb, sa);
@@ -124,41 +132,46 @@ __global__ __launch_bounds__(256) void k_lightmap_decode(const uint32_t* __restr
 
 // ---------------------------------------------------------------------------------------------------
 hipError_t launch_raymarch_light(const Geom& g, int half_store, const void* color, uint32_t* lightmap,
-	const FrameConsts& fc, const float* sh, uint32_t num_samples, hipStream_t s, unsigned long long* counters)
+	const FrameConsts& fc, const float* sh, uint32_t num_samples, hipStream_t s, unsigned long long* counters, int point_light)
 {
 	const dim3 grid((g.X + 63) / 64, (g.Y + 3) / 4, g.Zg), block(64, 4, 1);
-	if (half_store) hipLaunchKernelGGL(k_raymarch_light<true>, grid, block, 0, s, g, (const h16x4*)color, lightmap, fc, sh, num_samples, counters);
-	else hipLaunchKernelGGL(k_raymarch_light<false>, grid, block, 0, s, g, (const float4*)color, lightmap, fc, sh, num_samples, counters);
+#define FX_LAUNCH(H, P) hipLaunchKernelGGL((k_raymarch_light<H, P>), grid, block, 0, s, g, (const typename ColTex<H>::T*)color, lightmap, fc, sh, num_samples, counters)
+	if (half_store) { if (point_light) FX_LAUNCH(true, true); else FX_LAUNCH(true, false); }
+	else { if (point_light) FX_LAUNCH(false, true); else FX_LAUNCH(false, false); }
+#undef FX_LAUNCH
 	return hipGetLastError();
 }
 
 hipError_t launch_raymarch_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int cube_size, uint32_t mask, uint32_t num_samples,
-	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters, const DepthArgs* depth)
+	uint32_t num_light_samples, int separate, uint8_t* cube, hipStream_t s, unsigned long long* counters, const DepthArgs* depth, int point_light)
 {
 	const dim3 grid((cube_size + 7) / 8, (cube_size + 7) / 8, 6), block(8, 8, 1);
 	uint32_t* out = reinterpret_cast<uint32_t*>(cube);
-#define FX_LAUNCH(H, S) do { if (depth) hipLaunchKernelGGL((k_raymarch_view<H, S>), grid, block, 0, s, g, \
+#define FX_LAUNCH(H, S, P) do { if (depth) hipLaunchKernelGGL((k_raymarch_view<H, S, P>), grid, block, 0, s, g, \
 	(const typename ColTex<H>::T*)color, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters, *depth); \
-	else hipLaunchKernelGGL((k_raymarch_view<H, S>), grid, block, 0, s, g, \
+	else hipLaunchKernelGGL((k_raymarch_view<H, S, P>), grid, block, 0, s, g, \
 	(const typename ColTex<H>::T*)color, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters); } while (0)
-	if (half_store) { if (separate) FX_LAUNCH(true, true); else FX_LAUNCH(true, false); }
-	else { if (separate) FX_LAUNCH(false, true); else FX_LAUNCH(false, false); }
+	// (the separate-pass march only fetches the light map: one instantiation for both kinds of light)
+#define FX_PICK(H) do { if (separate) FX_LAUNCH(H, true, false); else if (point_light) FX_LAUNCH(H, false, true); else FX_LAUNCH(H, false, false); } while (0)
+	if (half_store) FX_PICK(true); else FX_PICK(false);
+#undef FX_PICK
 #undef FX_LAUNCH
 	return hipGetLastError();
 }
 
 hipError_t launch_raycast_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap,
 	const FrameConsts& fc, const float* sh, int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate,
-	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters, const DepthArgs* depth)
+	uint8_t* target, float* out_float, hipStream_t s, unsigned long long* counters, const DepthArgs* depth, int point_light)
 {
 	const dim3 grid((W + 7) / 8, (H + 7) / 8, 1), block(8, 8, 1);
 #define FX_ARGS(HF) g, (const typename ColTex<HF>::T*)color, lightmap, fc, sh, W, H, num_samples, num_light_samples, \
 	reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters
-#define FX_LAUNCH(HF, S) do { if (depth) hipLaunchKernelGGL((k_raycast_direct<HF, S>), grid, block, 0, s, FX_ARGS(HF), *depth); \
-	else hipLaunchKernelGGL((k_raycast_direct<HF, S>), grid, block, 0, s, FX_ARGS(HF)); } while (0)
-	if (half_store) { if (separate) FX_LAUNCH(true, true); else FX_LAUNCH(true, false); }
-	else { if (separate) FX_LAUNCH(false, true); else FX_LAUNCH(false, false); }
+#define FX_LAUNCH(HF, S, P) do { if (depth) hipLaunchKernelGGL((k_raycast_direct<HF, S, P>), grid, block, 0, s, FX_ARGS(HF), *depth); \
+	else hipLaunchKernelGGL((k_raycast_direct<HF, S, P>), grid, block, 0, s, FX_ARGS(HF)); } while (0)
+#define FX_PICK(HF) do { if (separate) FX_LAUNCH(HF, true, false); else if (point_light) FX_LAUNCH(HF, false, true); else FX_LAUNCH(HF, false, false); } while (0)
+	if (half_store) FX_PICK(true); else FX_PICK(false);
+#undef FX_PICK
 #undef FX_LAUNCH
 #undef FX_ARGS
 	return hipGetLastError();

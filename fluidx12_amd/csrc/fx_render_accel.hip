@@ -457,7 +457,8 @@ __global__ __launch_bounds__(256) void k_light_classify(const Geom g, const floa
 // pass 2: the shadow ray (:55) and the GI term (:59-68) of the listed voxels.  Every workgroup scans the plane counters into chunk
 // offsets (LDS), then wave w of the launch takes chunks w, w + W, ...: neighbours in the list -- rays of similar length -- go to
 // different waves, and nothing is dealt out through memory.
-template <bool COARSE>
+// POINT (here and in k_light_rays): the FX_LIGHT_POINT variant -- a voxel's shadow ray runs to the light point and ends there (fx_march.h)
+template <bool COARSE, bool POINT>
 __global__ __launch_bounds__(256) void k_light_march(const Geom g, const float* __restrict__ alpha, const float* __restrict__ occ,
 	const uint32_t* __restrict__ pos_mask, uint32_t mask_words, int msh, int MX, int MY, int CX, int CY,
 	const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ lightmap, const FrameConsts fc,
@@ -474,8 +475,8 @@ __global__ __launch_bounds__(256) void k_light_march(const Geom g, const float* 
 	__syncthreads();
 	const AccelVol<false, COARSE> vol{ nullptr, alpha, occ, lds, lds, msh, MX, MY, CX, CY };
 	const float stepScale = 3.46410155f / (float)numSamples;                       // RayMarch.hlsli:29-30
-	float lx, ly, lz;
-	light_dir_local(fc, lx, ly, lz);
+	float lx, ly, lz;                                                              // the light's direction; POINT: its place
+	if (POINT) light_point_local(fc, lx, ly, lz); else light_dir_local(fc, lx, ly, lz);
 	const uint32_t XY = (uint32_t)g.X * (uint32_t)g.Y;
 	for (uint32_t c = blockIdx.x * 4u + wave; c < T; c += gridDim.x * 4u) {
 		const uint32_t lo = find_segment(pre, Z, c);                               // the plane of chunk c
@@ -489,6 +490,11 @@ __global__ __launch_bounds__(256) void k_light_march(const Geom g, const float* 
 			const float oy = fmaf(((float)y + 0.5f) / (float)g.Y, 2.0f, -1.0f);
 			const float oz = fmaf(((float)z + 0.5f) / (float)g.Zg, 2.0f, -1.0f);
 			float shadow = 1.0f, ao = 1.0f, irr[3] = { 0.0f, 0.0f, 0.0f };
+			if (POINT) {                                                           // :49-50
+				float ex, ey, ez, tEnd;
+				point_light_ray(lx, ly, lz, ox, oy, oz, ex, ey, ez, tEnd);
+				cast_light_ray<kLightAhead, true>(shadow, g, vol, ox, oy, oz, ex, ey, ez, stepScale, numSamples, ns, tEnd);   // :55
+			} else
 			cast_light_ray<kLightAhead>(shadow, g, vol, ox, oy, oz, lx, ly, lz, stepScale, numSamples, ns);   // :55
 			if (sh) gi_term<kLightAhead>(irr, ao, g, vol, fc, sh, ox, oy, oz, fmaf(ox, 0.5f, 0.5f), fmaf(oy, 0.5f, 0.5f), fmaf(oz, 0.5f, 0.5f), stepScale, numSamples, ns);   // :59-68
 			lightmap[id] = light_value(fc, sh != nullptr, shadow, ao, irr);
@@ -508,7 +514,7 @@ __global__ __launch_bounds__(256) void k_light_march(const Geom g, const float* 
 // shadow up again and writes the light-map value).
 enum { RAYS_SHADOW = 0, RAYS_SHADOW_KEEP = 1, RAYS_AO = 2 };
 
-template <bool COARSE, int MODE>
+template <bool COARSE, int MODE, bool POINT>
 __global__ __launch_bounds__(1024) void k_light_rays(const Geom g, const float* __restrict__ alpha, const float* __restrict__ occ,
 	const uint32_t* __restrict__ pos_mask, uint32_t mask_words, int msh, int MX, int MY, int CX, int CY,
 	const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ lightmap, const FrameConsts fc,
@@ -526,8 +532,11 @@ __global__ __launch_bounds__(1024) void k_light_rays(const Geom g, const float* 
 	__syncthreads();
 	const AccelVol<false, COARSE> vol{ nullptr, alpha, occ, lds, lds, msh, MX, MY, CX, CY };
 	const float stepScale = 3.46410155f / (float)numSamples;                       // RayMarch.hlsli:29-30
-	float lx, ly, lz;                                                              // the ray's direction: the light's, or (RAYS_AO) the lane's own
-	light_dir_local(fc, lx, ly, lz);
+	static_assert(!(POINT && MODE == RAYS_AO), "the occlusion rays know no light");
+	float lx = 0.0f, ly = 0.0f, lz = 0.0f;                                         // the ray's direction: the light's, or (RAYS_AO, POINT) the lane's own
+	if (!POINT) light_dir_local(fc, lx, ly, lz);
+	float qx = 0.0f, qy = 0.0f, qz = 0.0f, tEnd = 0.0f;                            // POINT: the light's place (uniform) and where the lane's ray ends
+	if (POINT) light_point_local(fc, qx, qy, qz);
 	float rx = 0.0f, ry = 0.0f, rz = 0.0f;                                         // RAYS_AO: the direction before it was normalised
 	const uint32_t XY = (uint32_t)g.X * (uint32_t)g.Y;
 	const uint32_t W = gridDim.x * wpg;
@@ -573,6 +582,7 @@ __global__ __launch_bounds__(1024) void k_light_rays(const Geom g, const float* 
 					const float rd = rsqf(dot3(rx, ry, rz, rx, ry, rz));           // CSRayMarchL.hlsl:66
 					lx = rx * rd; ly = ry * rd; lz = rz * rd;
 				}
+				if (POINT) point_light_ray(qx, qy, qz, ox, oy, oz, lx, ly, lz, tEnd);   // CSRayMarchL.hlsl:49-50
 				live = true;
 			}
 			const uint32_t n = min(nidle, avail);
@@ -583,7 +593,7 @@ __global__ __launch_bounds__(1024) void k_light_rays(const Geom g, const float* 
 		for (int rep = 0; rep < FX_LIGHT_RAY_UNROLL; ++rep)
 		if (live) {                                                                // one sample of the loop :222-246
 			const float px = fmaf(lx, t, ox), py = fmaf(ly, t, oy), pz = fmaf(lz, t, oz);
-			bool on = i < numSamples && !outside(px, py, pz);
+			bool on = i < numSamples && (!POINT || t < tEnd) && !outside(px, py, pz);
 			if (on) {
 				++ns;
 				const Base b = make_base(g, fmaf(px, 0.5f, 0.5f), fmaf(py, 0.5f, 0.5f), fmaf(pz, 0.5f, 0.5f));
@@ -647,7 +657,7 @@ __global__ __launch_bounds__(256) void k_light_gi_dirs(const Geom g, const float
 }
 
 hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lightmap, const FrameConsts& fc, const float* sh,
-	uint32_t num_samples, hipStream_t s, unsigned long long* counters, bool filled)
+	uint32_t num_samples, hipStream_t s, unsigned long long* counters, bool filled, int point_light)
 {
 	const int ncell = a.CX * a.CY * a.CZ;
 	uint32_t* ctr = ctr_now(a, g);
@@ -665,25 +675,30 @@ hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lig
 	// threads x workgroups: 256 x 2048 0.118, 512 x 1024 0.113, 1024 x 512 0.118 ms)
 	const int ray_nt = FX_KNOB_INT("LIGHT_RAY_NT", 512);
 	const unsigned wgs = (unsigned)std::min<size_t>((cells + ray_nt - 1) / ray_nt, (size_t)FX_KNOB_INT("LIGHT_RAY_WGS", (int)kLightRayWorkgroups));
-#define FX_RAYS(C, M) hipLaunchKernelGGL((k_light_rays<C, M>), dim3(wgs), dim3(ray_nt), lds, s, g, a.alpha, a.occ, mask_pos(a), a.mask_words, a.msh, a.MX, a.MY, a.CX, a.CY, \
+#define FX_RAYS3(C, M, P) hipLaunchKernelGGL((k_light_rays<C, M, P>), dim3(wgs), dim3(ray_nt), lds, s, g, a.alpha, a.occ, mask_pos(a), a.mask_words, a.msh, a.MX, a.MY, a.CX, a.CY, \
 	a.list, ctr, lightmap, fc, a.gi, sh, num_samples, counters)
+#define FX_RAYS(C, M) FX_RAYS3(C, M, false)
+#define FX_SHADOW(C, M) do { if (point_light) FX_RAYS3(C, M, true); else FX_RAYS3(C, M, false); } while (0)
 	if (!sh) {
-		if (a.msh) FX_RAYS(true, RAYS_SHADOW); else FX_RAYS(false, RAYS_SHADOW);
+		if (a.msh) FX_SHADOW(true, RAYS_SHADOW); else FX_SHADOW(false, RAYS_SHADOW);
 		return hipGetLastError();
 	}
 	if (a.gi) {
-		if (a.msh) FX_RAYS(true, RAYS_SHADOW_KEEP); else FX_RAYS(false, RAYS_SHADOW_KEEP);
+		if (a.msh) FX_SHADOW(true, RAYS_SHADOW_KEEP); else FX_SHADOW(false, RAYS_SHADOW_KEEP);
 		hipLaunchKernelGGL(k_light_gi_dirs, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 2048)), dim3(256), ((size_t)g.Zg + 1) * 4, s, g, a.alpha, a.CX, a.CY,
 			a.list, ctr, a.gi, counters);
 		if (a.msh) FX_RAYS(true, RAYS_AO); else FX_RAYS(false, RAYS_AO);
 		return hipGetLastError();
 	}
+#undef FX_SHADOW
 #undef FX_RAYS
+#undef FX_RAYS3
 	// (no scratch for the occlusion rays' directions: the chunked march, a wave per 64 listed voxels)
-	if (a.msh) hipLaunchKernelGGL(k_light_march<true>, dim3(wgs), dim3(256), lds, s, g, a.alpha, a.occ, mask_pos(a), a.mask_words, a.msh, a.MX, a.MY, a.CX, a.CY,
-		a.list, ctr, lightmap, fc, sh, num_samples, counters);
-	else hipLaunchKernelGGL(k_light_march<false>, dim3(wgs), dim3(256), lds, s, g, a.alpha, a.occ, mask_pos(a), a.mask_words, a.msh, a.MX, a.MY, a.CX, a.CY,
-		a.list, ctr, lightmap, fc, sh, num_samples, counters);
+#define FX_MARCH(C, P) hipLaunchKernelGGL((k_light_march<C, P>), dim3(wgs), dim3(256), lds, s, g, a.alpha, a.occ, mask_pos(a), a.mask_words, a.msh, a.MX, a.MY, a.CX, a.CY, \
+	a.list, ctr, lightmap, fc, sh, num_samples, counters)
+	if (a.msh) { if (point_light) FX_MARCH(true, true); else FX_MARCH(true, false); }
+	else { if (point_light) FX_MARCH(false, true); else FX_MARCH(false, false); }
+#undef FX_MARCH
 	return hipGetLastError();
 }
 
@@ -707,7 +722,8 @@ __device__ __forceinline__ AccelVol<HALF, COARSE> view_volume(uint32_t* lds, con
 }
 
 // Dep (here and below): empty, or the scene depth (fx_march.h cube_tmax / direct_tmax)
-template <bool HALF, bool SEPARATE, bool COARSE, class... Dep>
+// POINT (the merged marches): the FX_LIGHT_POINT variant of the nested light rays (fx_march.h march_ray)
+template <bool HALF, bool SEPARATE, bool COARSE, bool POINT, class... Dep>
 __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, const float* __restrict__ alpha,
 	const float* __restrict__ occ, const MaskArgs m, const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh,
 	int size, uint32_t mask, uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ cube, unsigned long long* __restrict__ counters,
@@ -724,7 +740,7 @@ __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename
 	const AccelVol<HALF, COARSE> vol = view_volume<HALF, SEPARATE, COARSE>(lds, col, alpha, occ, m, __syncthreads_or(go) != 0);
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
-	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
+	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1, POINT>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	if (!go) return;
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :192
@@ -733,7 +749,7 @@ __global__ __launch_bounds__(256) void k_view_march(const Geom g, const typename
 }
 
 // direct screen-space march (row f-2; PSRayCast.hlsl:44-127 / PSRayCastV.hlsl): 16 x 16 pixels per workgroup
-template <bool HALF, bool SEPARATE, bool COARSE, class... Dep>
+template <bool HALF, bool SEPARATE, bool COARSE, bool POINT, class... Dep>
 __global__ __launch_bounds__(256) void k_direct_march(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, const float* __restrict__ alpha,
 	const float* __restrict__ occ, const MaskArgs m, const uint32_t* __restrict__ lightmap, const FrameConsts fc, const float* __restrict__ sh,
 	int W, int H, uint32_t numSamples, uint32_t numLightSamples, uint32_t* __restrict__ target, float4* __restrict__ out_float,
@@ -751,7 +767,7 @@ __global__ __launch_bounds__(256) void k_direct_march(const Geom g, const typena
 	float sr, sg, sb, sa;
 	uint32_t nv = 0, nl = 0, nm = 0;
 	const float tMax = go ? direct_tmax(fc, px, py, W, H, o, d, dep...) : 3.40282347e+38f;   // PSRayCast.hlsl:52-56
-	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
+	march_ray<AccelVol<HALF, COARSE>, SEPARATE, SEPARATE ? kViewAhead : 1, POINT>(g, vol, lightmap, fc, sh, o, d, tMax, numSamples, numLightSamples, go, sr, sg, sb, sa, nv, nl, nm);
 	flush_counts(counters, nv, nl, nm);
 	if (!go) return;
 	sr *= 0.159154937f; sg *= 0.159154937f; sb *= 0.159154937f;                    // :124
@@ -958,7 +974,7 @@ static MaskArgs mask_args(const RenderAccel& a) { return MaskArgs{ mask_pos(a), 
 
 hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int cube_size, uint32_t mask, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* cube, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters, const DepthArgs* depth)
+	unsigned long long* counters, const DepthArgs* depth, int point_light)
 {
 	const dim3 grid((cube_size + 15) / 16, (cube_size + 15) / 16, 6), block(256);
 	const size_t lds = (size_t)a.mask_words * 4 * (separate ? 1 : 2);
@@ -983,10 +999,13 @@ hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, c
 		return hipGetLastError();
 	}
 #define FX_ARGS(H) g, (const typename ColTex<H>::T*)color, a.alpha, a.occ, m, lightmap, fc, sh, cube_size, mask, num_samples, num_light_samples, out, counters
-#define FX_LAUNCH(H, S, C) do { if (depth) hipLaunchKernelGGL((k_view_march<H, S, C>), grid, block, lds, s, FX_ARGS(H), *depth); \
-	else hipLaunchKernelGGL((k_view_march<H, S, C>), grid, block, lds, s, FX_ARGS(H)); } while (0)
-#define FX_PICK(H, S) do { if (a.msh) FX_LAUNCH(H, S, true); else FX_LAUNCH(H, S, false); } while (0)
-	if (half_store) FX_PICK(true, false); else FX_PICK(false, false);              // the merged march: its samples cast rays of their own
+#define FX_LAUNCH(H, S, C, P) do { if (depth) hipLaunchKernelGGL((k_view_march<H, S, C, P>), grid, block, lds, s, FX_ARGS(H), *depth); \
+	else hipLaunchKernelGGL((k_view_march<H, S, C, P>), grid, block, lds, s, FX_ARGS(H)); } while (0)
+	// merged marches (SEPARATE = false) come per kind of light; a separate-pass march only fetches the light map: one instantiation
+#define FX_MERGED(H, C) do { if (point_light) FX_LAUNCH(H, false, C, true); else FX_LAUNCH(H, false, C, false); } while (0)
+#define FX_PICK_MERGED(H) do { if (a.msh) FX_MERGED(H, true); else FX_MERGED(H, false); } while (0)
+#define FX_PICK_SEPARATE(H) do { if (a.msh) FX_LAUNCH(H, true, true, false); else FX_LAUNCH(H, true, false, false); } while (0)
+	if (half_store) FX_PICK_MERGED(true); else FX_PICK_MERGED(false);              // the merged march: its samples cast rays of their own
 #undef FX_LAUNCH
 #undef FX_ARGS
 	return hipGetLastError();
@@ -994,22 +1013,24 @@ hipError_t launch_accel_view(const Geom& g, int half_store, const void* color, c
 
 hipError_t launch_accel_direct(const Geom& g, int half_store, const void* color, const uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	int W, int H, uint32_t num_samples, uint32_t num_light_samples, int separate, uint8_t* target, float* out_float, const RenderAccel& a, hipStream_t s,
-	unsigned long long* counters, const DepthArgs* depth)
+	unsigned long long* counters, const DepthArgs* depth, int point_light)
 {
 	const dim3 grid((W + 15) / 16, (H + 15) / 16, 1), block(256);
 	const size_t lds = (size_t)a.mask_words * 4 * (separate ? 1 : 2);
 	const MaskArgs m = mask_args(a);
 #define FX_ARGS(HF) g, (const typename ColTex<HF>::T*)color, a.alpha, a.occ, m, lightmap, fc, sh, W, H, num_samples, num_light_samples, \
 	reinterpret_cast<uint32_t*>(target), reinterpret_cast<float4*>(out_float), counters
-#define FX_LAUNCH(HF, S, C) do { if (depth) hipLaunchKernelGGL((k_direct_march<HF, S, C>), grid, block, lds, s, FX_ARGS(HF), *depth); \
-	else hipLaunchKernelGGL((k_direct_march<HF, S, C>), grid, block, lds, s, FX_ARGS(HF)); } while (0)
+#define FX_LAUNCH(HF, S, C, P) do { if (depth) hipLaunchKernelGGL((k_direct_march<HF, S, C, P>), grid, block, lds, s, FX_ARGS(HF), *depth); \
+	else hipLaunchKernelGGL((k_direct_march<HF, S, C, P>), grid, block, lds, s, FX_ARGS(HF)); } while (0)
 	// one lane per pixel for both variants: two million rays, most of them beside the volume, keep every SIMD busy without the
 	// eight-lanes-per-ray scheme (measured at 1920x1080 / 256^3: 0.33 ms either way, 0.47 ms with it)
-	if (half_store) { if (separate) FX_PICK(true, true); else FX_PICK(true, false); }
-	else { if (separate) FX_PICK(false, true); else FX_PICK(false, false); }
+	if (half_store) { if (separate) FX_PICK_SEPARATE(true); else FX_PICK_MERGED(true); }
+	else { if (separate) FX_PICK_SEPARATE(false); else FX_PICK_MERGED(false); }
 #undef FX_LAUNCH
 #undef FX_ARGS
-#undef FX_PICK
+#undef FX_PICK_SEPARATE
+#undef FX_PICK_MERGED
+#undef FX_MERGED
 	return hipGetLastError();
 }
 

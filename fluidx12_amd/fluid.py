@@ -203,6 +203,34 @@ class Fluid:
                    "SetSceneDepth")
         self._depth_ref = None
 
+    def SetLight(self, position, kind="directional", color=None, ambient=None):
+        """the scene light of the following renders (fx_set_light).  position: world space of UpdateFrame's view matrix (the volume is
+        [-10, 10]^3 there); kind "directional": only its direction matters, "point": the light's place -- shadow rays run to it and end
+        there.  color / ambient: (r, g, b, intensity); None keeps the current one.  SetLight(None): the reference's constants again.
+        Render state: kept across UpdateFrame, not stored in checkpoints."""
+        self._need()
+        if position is None:
+            capi.check(self._lib.fx_set_light(self._ctx, None), "SetLight")
+            return
+        l = capi.Light()
+        capi.check(self._lib.fx_get_light(self._ctx, C.byref(l)), "SetLight")
+        l.struct_size = C.sizeof(capi.Light)
+        l.kind = {"directional": capi.LIGHT_DIRECTIONAL, "point": capi.LIGHT_POINT}[kind]
+        l.position = (C.c_float * 3)(*[float(v) for v in position])
+        if color is not None:
+            l.color = (C.c_float * 4)(*[float(v) for v in color])
+        if ambient is not None:
+            l.ambient = (C.c_float * 4)(*[float(v) for v in ambient])
+        capi.check(self._lib.fx_set_light(self._ctx, C.byref(l)), "SetLight")
+
+    def GetLight(self):
+        """the light in force (fx_get_light): {"kind", "position", "color", "ambient"}"""
+        self._need()
+        l = capi.Light()
+        capi.check(self._lib.fx_get_light(self._ctx, C.byref(l)), "GetLight")
+        return {"kind": "point" if l.kind == capi.LIGHT_POINT else "directional", "position": tuple(l.position), "color": tuple(l.color),
+                "ambient": tuple(l.ambient)}
+
     # ---- the demo driver's time-step rule (FluidX12.cpp:266) ---------------------------------------
     def default_time_step(self):
         X, Y, Z = self.grid

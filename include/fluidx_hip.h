@@ -189,6 +189,34 @@ int fx_render_cube(fx_ctx* ctx, void* stream, uint8_t frame_index);
 int fx_set_scene_depth(fx_ctx* ctx, void* stream, const float* depth, uint32_t width, uint32_t height,
 	float z_near, float z_far, uint32_t flags);
 
+/* The scene light of the following renders.  A context starts with the reference's constants (Fluid.cpp:169-173: position (75, 75, -75),
+ * colour (1, .7, .3) x 3 pi, ambient (1, 1, 1) x 1.5 pi, directional); fx_set_light(ctx, NULL) returns to them.
+ *   position  world space of fx_update_frame's view matrix; the volume is the cube [-10, 10]^3 there (its world matrix is a scale by 10)
+ *   FX_LIGHT_DIRECTIONAL  only the direction of `position` matters: every shadow ray runs along normalize(position) (CSRayMarchL.hlsl:52-53)
+ *   FX_LIGHT_POINT        `position` is the light's place (the reference's compiled-out _POINT_LIGHT_ variants): the shadow ray of a light-map
+ *                         voxel (CSRayMarchL.hlsl:49-50) and the nested light ray of each visible sample of the merged marches
+ *                         (CSRayMarch.hlsl:165, PSRayCast.hlsl:93) run from there towards the light.  Two deviations from that variant text:
+ *                         (A) the ray ENDS at the light -- a sample is taken only while t < |light - origin| -- so smoke behind a lamp does
+ *                         not shadow what is in front of it (the variant marches on through the light); (B) where the light sits exactly
+ *                         on a ray's origin (a light vector of length zero, or not finite) no shadow ray is cast: shadow = 1.
+ *                         No distance attenuation (the reference has none).
+ *   color, ambient        rgb x intensity (w); ambient is unused while a light probe is set (fx_set_sh), as in the reference
+ * GI / occlusion rays, the unlit constant `light colour + ambient`, step rule and thresholds are the same for both kinds.
+ * The light is render state like the scene depth: per context, kept across fx_update_frame, in force at the next fx_render, not checkpointed,
+ * not digested; FX_FLAG_RENDER_ONLY contexts take it too.
+ * FX_E_INVALID (the previous light stays in force): null context, wrong struct_size, unknown kind, a component that is not finite, a negative
+ * colour or ambient component (the light map is unsigned R11G11B10_FLOAT), a directional light at (0, 0, 0), 2-D grid, slab context. */
+#define FX_LIGHT_DIRECTIONAL 0u
+#define FX_LIGHT_POINT       1u
+typedef struct fx_light {
+	uint32_t struct_size, kind;
+	float position[3];
+	float color[4];
+	float ambient[4];
+} fx_light;
+int fx_set_light(fx_ctx* ctx, const fx_light* light);
+int fx_get_light(fx_ctx* ctx, fx_light* out);
+
 /* The light probe's sky pass (LightProbe::RenderEnvironment, LightProbe.cpp:85-97; PSEnvironment.hlsl), which the demo draws
  * before the volume (FluidX12.cpp:483): fx_set_environment keeps a copy of the radiance cube float[6][n][n][3] on the device
  * (NULL releases it), fx_render_environment writes it onto the render target as seen by the camera of the last

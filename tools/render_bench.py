@@ -2,11 +2,12 @@
 library's own HIP-event marks.  Run on the GPU box (optionally under tools/kstats.sh for per-kernel times):
 
     python3 tools/render_bench.py [--grid 256] [--frame 132] [--storage fp32] [--sh] [--reps 5] [--modes 1,0] [--flags optimized,merged,direct]
-                                  [--depth none|far|plane]
+                                  [--depth none|far|plane] [--light point:x,y,z | directional:x,y,z]
 
 --depth attaches a scene depth (fx_set_scene_depth): `far` a cleared buffer (1.0: nothing occludes), `plane` the fronto-parallel plane through
 the volume's centre, which cuts the plume in half.  Each run also reports the view rays' colour samples of one counted render
-(FX_OPT_COUNT_SAMPLES, outside the timed renders).
+(FX_OPT_COUNT_SAMPLES, outside the timed renders).  --light sets the scene light (fx_set_light; world space, the volume is [-10, 10]^3): with
+`point:` the light pass and the merged marches run their point-light kernels.
 """
 import argparse
 import json
@@ -31,7 +32,17 @@ def main():
     ap.add_argument("--flags", default="optimized")
     ap.add_argument("--viewport", default="1920x1080")
     ap.add_argument("--depth", default="none", choices=("none", "far", "plane"))
+    ap.add_argument("--light", default=None, help="point:x,y,z or directional:x,y,z (default: the reference's constants)")
     a = ap.parse_args()
+    light = None
+    if a.light:
+        kind, _, xyz = a.light.partition(":")
+        try:
+            light = (kind, [float(v) for v in xyz.split(",")])
+        except ValueError:
+            light = (kind, [])
+        if kind not in ("point", "directional") or len(light[1]) != 3:
+            ap.error("--light takes point:x,y,z or directional:x,y,z, got %r" % a.light)
     W, H = (int(v) for v in a.viewport.split("x"))
     G = a.grid
     f = fx.Fluid()
@@ -51,10 +62,12 @@ def main():
         zv = float(np.linalg.norm(eye))                 # the camera looks at the volume's centre: view-space z of the plane through it
         z = 1.0 if a.depth == "far" else P[2, 2] + P[3, 2] / zv
         f.SetSceneDepth(np.full((H, W), z, np.float32))
+    if light:
+        f.SetLight(light[1], light[0])
     f.Synchronize()
     flagmap = {"optimized": fx.Fluid.OPTIMIZED, "merged": fx.Fluid.RAY_MARCH_CUBEMAP, "direct": fx.Fluid.SEPARATE_LIGHT_PASS,
                "direct_merged": fx.Fluid.RAY_MARCH_DIRECT}
-    out = {"grid": G, "frame": a.frame, "storage": a.storage, "sh": a.sh, "depth": a.depth, "runs": []}
+    out = {"grid": G, "frame": a.frame, "storage": a.storage, "sh": a.sh, "depth": a.depth, "light": a.light, "runs": []}
     pics = {}
     for mode in (int(m) for m in a.modes.split(",")):
         f.set_option(capi.OPT_RENDER_ACCEL, mode)
