@@ -147,6 +147,25 @@ hipError_t launch_jacobi(const Geom& g, JacobiLaunch l, const float* p_in, const
 // the interior launches of an overlapped round of n slab ranks: sweeps per launch, and the lengths of a round of cnt sweeps (at most cnt)
 int jacobi_group_sweeps(const JacobiPolicy* p, int n);
 int jacobi_group_parts(const JacobiPolicy& lead, int t, int cnt, int* parts);
+// ---- the launches of the faithful solve (fx_jacobi_plan.cpp decides, fx_schedule.cpp: jacobi_freeze runs them)
+const int kFreezeHalo = 4;                          // planes a slab rank exchanges behind every launch = the most levels a tile launch takes (jacobi_freeze_levels_per_launch)
+// masks: the context holds the byte mask and the tile-mark buffer; slab: it is a rank of a chain whose thinnest slab has min_nz planes
+bool freeze_takes_sparse_solver(const Geom& g, uint32_t iters, bool masks, bool slab, int min_nz);
+// FZ_DENSE: the dense sweep writing both copies of level 1, FZ_DENSE_ONE: one (a strip launch follows); FZ_STRIP: a masked strip launch of
+// 4 or 3 levels for every cell; FZ_TILES: a launch of up to 4 levels over the tiles that still relax.  base: the level the launch starts from
+enum FreezeKind { FZ_DENSE = 0, FZ_DENSE_ONE, FZ_STRIP, FZ_TILES };
+struct FreezeLaunch { int kind, levels, base; };
+// the launches of a solve in order (the levels sum to iters) -> how many, at most kFreezeSlots (0: they do not fit); strips_in_use: the context's fz_dense_n
+int freeze_plan(const Geom& g, uint32_t iters, bool slab, bool third_mask, int strips_in_use, FreezeLaunch* out);
+// levels per strip launch (4 / 3; 0: no strip pipeline); *forced: FREEZE_DENSE_LEVELS -- the levels the strip pipelines take, below 0: as many
+// launches as the count of relaxing tiles asks for (the two functions below)
+int freeze_strip_width(const Geom& g, bool slab, bool third_mask, int* forced);
+// what the solve of generation gen does about that count -- count: launch k_count_marks behind its dense sweep, take_over: read the count
+// launched two solves ago
+struct FreezeCadence { bool count, take_over; };
+FreezeCadence freeze_cadence(uint32_t gen);
+// strip launches in use, n -> n', once a count is taken over: `active` of `tiles` tiles relax; four: a strip launch takes four levels, not three
+int freeze_strip_hysteresis(int n, uint32_t active, uint32_t tiles, bool four);
 // The LDS hand-overs of the strip kernels wait in bounded loops; a wait that runs out raises a device word (per translation unit) instead
 // of hanging the device or continuing silently.  Read-and-clear on the current device; fx_synchronize turns a raised word into FX_E_DEVICE.
 // fx_field_digest's kernel: two wrapping sums of 64-bit mixes of (stored bits, key0 + element index) over `count` elements, added to out[0..1]

@@ -3,6 +3,8 @@
 // jacobi_plan turns it into the launches of a round, launch_jacobi hands a planned launch to its family's launcher, jacobi_group_* is the form
 // the overlapped slab schedule uses.  The families' own predicates (jacobi_*_supported) and launchers stay with their kernels.
 // tests/test_jacobi_plan.py pins the schedule of some five thousand (geometry, request, switch, count) cases (tests/golden/jacobi_plan.json).
+// The faithful solve's policy is here too (freeze_*, at the end): whether the sparse solver runs, how many strip launches follow the dense
+// sweep, the launches of a solve and the cadence of the activity count; tests/test_freeze_plan.py pins it (tests/golden/freeze_plan.json).
 #include "fx_internal.h"
 #include <algorithm>
 
@@ -147,6 +149,70 @@ int jacobi_group_parts(const JacobiPolicy& lead, int t, int cnt, int* parts)
 	for (int left = cnt % t; left > 0; left -= parts[m++]) parts[m] = legal_launch(lead, left).sweeps;
 	for (int j = 0; j < cnt / t; ++j) parts[m++] = t;
 	return m;
+}
+
+// ---- the faithful solve (FX_JACOBI_FAITHFUL: the sparse solver of fx_jacobi_freeze.hip; fx_schedule.cpp: jacobi_freeze runs what is planned here)
+// Whether it runs at all: the context holds the byte mask and the tile marks, the kernels serve the geometry, a level fits the stat word's low
+// byte and every launch has its counters.  On a slab rank chain-wide facts only -- every rank must take the same branch: the grid, the halo,
+// the thinnest slab.
+bool freeze_takes_sparse_solver(const Geom& g, uint32_t iters, bool masks, bool slab, int min_nz)
+{
+	if (!(masks && jacobi_freeze_supported(g) && iters <= 255 && (int)iters / jacobi_freeze_levels_per_launch() + 3 < kFreezeSlots)) return false;
+	const uint64_t planes = (uint64_t)g.Zg + 2 * (uint64_t)g.H;
+	return !slab || (g.H >= kFreezeHalo && min_nz >= kFreezeHalo && (uint64_t)g.X * g.Y * planes < (1u << 30));
+}
+
+// the levels a masked strip launch takes behind the dense sweep: 4 where the octet serves the grid (k_freeze_strip4o, fx_jacobi_strip4.hip;
+// FREEZE_STRIP4=0: never), else 3 (k_freeze_strip3, fx_jacobi_stripm.hip); 0: no strip pipeline -- single domain, X = 256 and a third mask
+// buffer to rotate through.  *forced = FREEZE_DENSE_LEVELS: how many levels go through the strip pipelines (0, 3, 4, 6, 7, 8 ...); default
+// -1 = by what the dense sweeps of the last steps left relaxing (freeze_strip_hysteresis)
+int freeze_strip_width(const Geom& g, bool slab, bool third_mask, int* forced)
+{
+	*forced = FX_KNOB_INT("FREEZE_DENSE_LEVELS", -1);
+	if (slab || !third_mask || !jacobi_freeze_strip_supported(g)) return 0;
+	return FX_KNOB_INT("FREEZE_STRIP4", 1) && jacobi_freeze_strip4_supported(g) ? 4 : 3;
+}
+
+// Every fourth solve counts the tiles its dense sweep left relaxing (the plume changes slowly, the count is a 5-us launch); the solve TWO
+// after it takes the count over, behind the event recorded with it -- by then it has long arrived, so nothing waits, and which solve switches
+// is a function of the step sequence, not of when the host happened to look (the unsynchronised read made launch sequences, step
+// times and kernel statistics vary from run to run around the threshold)
+FreezeCadence freeze_cadence(uint32_t gen) { return FreezeCadence{ (gen & 3u) == 0u, (gen & 3u) == 2u }; }
+
+// How many strip launches a solve takes (n in use -> n'), from the relaxing tiles among all, with hysteresis.  Young plumes stay on the tile
+// launches, where a masked launch would cost 0.08 ms for nothing.
+int freeze_strip_hysteresis(int n, uint32_t active, uint32_t tiles, bool four)
+{
+	if (four) {
+		// four levels per launch (k_freeze_strip4o behind a one-copy dense sweep): one launch pays from a fifth of the tiles (256^3 plume: frame
+		// ~70, 0.600 -> 0.585 ms per step; at a half, frame 110: 0.747 -> 0.671), a second one from two thirds (frame ~140; frame 190: 0.790 -> 0.759)
+		if (n == 0 && 5u * active >= tiles) n = 1;
+		else if (n >= 1 && 6u * active < tiles) n = 0;
+		if (n == 1 && 16u * active >= 11u * tiles) n = 2;
+		else if (n == 2 && 8u * active < 5u * tiles) n = 1;
+	} else                                                              // three levels per launch (k_freeze_strip3, 30 us per level): one launch from
+		n = n == 0 ? 2u * active >= tiles : 5u * active >= 2u * tiles;      // half of the tiles, none again below two fifths
+	return n;
+}
+
+// The launches of one solve of `iters` levels, in order: the dense sweep (level 1 everywhere), strip launches of four or three levels
+// (7 = 4 + 3, 11 = 4 + 4 + 3; a strip launch needs a level left behind it for the tile launches), then tile launches of up to FREEZE_T levels
+// over the tiles that still relax.  While most tiles relax the tile launches are dense sweeps in all but name (43 us per level at 256^3, a cone
+// five times the core per tile) against 22 (fours) / 30 (threes) us per level on the strips.  A strip launch reads ONE copy of level 1, so
+// the dense sweep in front of one leaves its second copy away (FZ_DENSE_ONE; FREEZE_DENSE_ONE=0: writes both as in front of tile launches).
+// strips_in_use: the context's hysteresis state.  -> how many launches (<= kFreezeSlots wherever freeze_takes_sparse_solver holds)
+int freeze_plan(const Geom& g, uint32_t iters, bool slab, bool third_mask, int strips_in_use, FreezeLaunch* out)
+{
+	int forced, level = 1, left = (int)iters - 1, m = 1;
+	const int width = freeze_strip_width(g, slab, third_mask, &forced), T = jacobi_freeze_levels_per_launch();
+	for (int want = !width ? 0 : forced < 0 ? strips_in_use * width : forced; left > 0 && m < kFreezeSlots; ++m) {
+		const bool strip = want >= 3 && left > 3;                           // (never again once it fails: want and left only fall)
+		const int lv = !strip ? std::min(T, left) : width == 4 && want >= 4 && left > 4 ? 4 : 3;
+		out[m] = FreezeLaunch{ strip ? FZ_STRIP : FZ_TILES, lv, level };
+		level += lv; left -= lv; want -= lv;
+	}
+	out[0] = FreezeLaunch{ m > 1 && out[1].kind == FZ_STRIP && FX_KNOB_INT("FREEZE_DENSE_ONE", 1) ? FZ_DENSE_ONE : FZ_DENSE, 1, 0 };
+	return left > 0 ? 0 : m;                                            // (0: more launches than a solve has counters for -- freeze_takes_sparse_solver refuses those)
 }
 
 }  // namespace fx

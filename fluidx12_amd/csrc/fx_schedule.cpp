@@ -349,34 +349,36 @@ static int clear_freeze_masks(std::vector<fx_ctx*>& M, hipStream_t s)
 	return FX_OK;
 }
 
-// FX_JACOBI_FAITHFUL: the sparse solver of fx_jacobi_freeze.hip.  Level 1 everywhere (into p[other] AND p_aux; the input buffer
-// becomes the spare), then ceil((iters - 1) / T) launches over the tiles that still relax, all enqueued; the result is in the last
-// launch's output buffer (settled tiles agree in both).  Bit-identical to `iters` generic sweeps with the byte mask
+// FX_JACOBI_FAITHFUL: the sparse solver of fx_jacobi_freeze.hip, as fx_jacobi_plan.cpp plans it (freeze_plan): level 1 everywhere, then
+// masked strip launches for every cell while most tiles relax, then launches over the tiles that still do, all enqueued; the result is in
+// the last launch's output buffer (settled tiles agree in both).  Bit-identical to `iters` generic sweeps with the byte mask
 // (tests/test_gpu_freeze.py).  A slab rank (round 4) runs it on the view of the planes it holds (jacobi_freeze_view): the dense sweep
 // over its owned planes, the tile cones reaching into the halo, and kFreezeHalo planes of pressure + mask travelling to the
 // neighbours behind every launch -- every rank enqueues the same launches and exchanges whatever its tiles do.
-// (a level fits the stat word's low byte, every launch has its counters)
-static const int kFreezeHalo = 4;                          // = the most levels a tile launch takes (jacobi_freeze_levels_per_launch)
-static bool takes_sparse_solver(const fx_ctx* c, uint32_t iters)
-{
-	if (!(c->frozen && c->fz_tile_next && jacobi_freeze_supported(c->g) && iters <= 255 && (int)iters / jacobi_freeze_levels_per_launch() + 3 < kFreezeSlots)) return false;
-	if (!multi_rank(c)) return true;
-	// chain-wide facts only (every rank must take the same branch): the grid, the halo, the thinnest slab
-	const uint64_t planes = (uint64_t)c->g.Zg + 2 * (uint64_t)c->g.H;
-	return c->g.H >= kFreezeHalo && c->group->min_nz >= kFreezeHalo && (uint64_t)c->g.X * c->g.Y * planes < (1u << 30);
-}
+// (The dense sweep in front of tile launches writes level 1 to BOTH buffers they alternate between.  Writing one and letting the first
+// tile launch carry the unlisted tiles' border cells across was built and measured level: the dense sweep 75 -> 46 us at 256^3, the
+// first tile launch slower by as much -- the shell of a 4-deep cone around ~3000 listed tiles is more bytes than the second copy.)
+// Whole steps (simulate_impl) leave the divergence to the dense sweep: it computes b from the advected velocity and stores it for the
+// launches behind it, instead of reading it back from a launch of its own.
+// fx_timing books the dense sweep as the "main" launch and the launches behind it beside it.  A single domain keeps ONE mark open over
+// all of them (an event record between two launches is a 2-3 us gap, 17 of them a solve); slab ranks close it at every exchange.
+static bool takes_sparse_solver(const fx_ctx* c, uint32_t iters) { return freeze_takes_sparse_solver(c->g, iters, c->frozen && c->fz_tile_next, multi_rank(c), multi_rank(c) ? c->group->min_nz : 0); }
+
+// the buffers behind a launch that read `a`: a tile launch left its last level in d; a strip launch in d AND the spare, and the buffer it
+// read is the spare now
+template <class T> static void freeze_rotate(T*& a, T*& d, T*& spare, bool strip) { std::swap(a, d); if (strip) std::swap(d, spare); }
 
 static int jacobi_freeze(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters)
 {
 	fx_ctx* ctx = lead;                                                 // FX_HIP reports through `ctx`
 	const bool multi = multi_rank(lead);
-	struct Run { Geom v; size_t off; int own0; FreezeWork w; float *src, *a, *d; uint8_t *ma, *md, *mx; uint32_t* stat; uint32_t stat_hi; };
+	struct Run { Geom v; size_t off, moff; int own0; FreezeWork w; float *src, *a, *d; uint8_t *ma, *md, *mx; uint32_t* stat; uint32_t stat_hi; };
 	std::vector<Run> R(M.size());
 	std::vector<std::unique_ptr<ScopedMark>> mk(M.size());
 	const bool fuse = lead->fz_fuse_div;
 	lead->fz_fuse_div = false;
-	int strip_want = 0;                                                 // levels wanted from the masked strip pipelines (single domain, X = 256)
-	bool strip_four = false, count_marks_now = false;
+	FreezeLaunch plan[kFreezeSlots];                                    // (the same on every rank of a chain: no strips there, and the tile launches follow from iters alone)
+	int launches = 0;
 	for (size_t i = 0; i < M.size(); ++i) {
 		fx_ctx* m = M[i];
 		DeviceGuard dg(m->device);
@@ -391,71 +393,41 @@ static int jacobi_freeze(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, u
 		int first = 0;
 		r.v = jacobi_freeze_view(m->g, &first, &r.own0);
 		r.off = (size_t)first * m->g.plane();
+		r.moff = (size_t)first * (size_t)((m->g.X + 3) / 4) * m->g.Y;
 		const uint32_t gen = m->fz_gen;
 		r.stat_hi = gen << 8;
 		r.stat = m->fz_stat + gen % kFreezeStatRing;
 		m->fz_iters[gen % kFreezeStatRing] = iters;
-		const size_t cw = jacobi_freeze_count_words();
+		const size_t cw = jacobi_freeze_count_words(), es = elem_size(m);
 		r.w = FreezeWork{ m->fz_tile_next, gen, { m->fz_list[0], m->fz_list[1] }, jacobi_freeze_tiles(m->g),
 			m->fz_counts + (gen & 1u) * cw, m->fz_counts + ((gen & 1u) ^ 1u) * cw };
 		r.src = m->p[m->p_cur]; r.a = m->p[m->p_cur ^ 1]; r.d = m->p_aux;
 		r.ma = m->fz_mask[0]; r.md = m->fz_mask[1]; r.mx = m->fz_mask[2];
-		// (The dense sweep writes level 1 to BOTH buffers the tile launches alternate between.  Writing one and letting the first tile
-		// launch carry the unlisted tiles' border cells across was built and measured level: the dense sweep 75 -> 46 us at 256^3, the
-		// first tile launch slower by as much -- the shell of a 4-deep cone around ~3000 listed tiles is more bytes than the second copy.)
-		// whole steps (simulate_impl) leave the divergence to this launch: it computes b from the advected velocity and stores it for the
-		// tile launches, instead of reading it back from a launch of its own
-		const size_t moff = (size_t)first * (size_t)((m->g.X + 3) / 4) * m->g.Y, es = elem_size(m);
-		// fx_timing books the dense sweep as the "main" launch and the tile launches beside it.  A single domain keeps ONE mark open over
-		// all of them (an event record between two launches is a 2-3 us gap, 17 of them a solve); slab ranks close it at every exchange
-		// While most tiles still relax the tile launches are dense sweeps in all but name: the levels right behind the dense sweep then go
-		// through a masked strip pipeline (see below), decided HERE because the dense sweep itself depends on it -- a strip launch reads one
-		// copy of level 1 and writes both buffers, so the dense sweep in front of it leaves its second copy (and second mask copy) away.
-		// FREEZE_DENSE_LEVELS: how many levels (0, 3, 4, 6, 7, 8 ...); default -1 = by what the dense sweeps of the last steps left relaxing
-		// -- the count k_count_marks put into a host-visible word behind an earlier solve's dense sweep (thresholds below).  Young plumes
-		// stay on the tile launches, where a masked launch would cost 0.08 ms for nothing.
-		if (!multi && jacobi_freeze_strip_supported(m->g) && m->fz_mask[2]) {
-			strip_want = FX_KNOB_INT("FREEZE_DENSE_LEVELS", -1);
-			strip_four = FX_KNOB_INT("FREEZE_STRIP4", 1) && jacobi_freeze_strip4_supported(m->g);
-			if (strip_want < 0) {
-				strip_want = 0;
-				if (m->fz_active_dev) {
-					// every fourth solve counts (the plume changes slowly, the count is a 5-us launch); the solve TWO after it takes the count over,
-					// behind the event recorded with it -- by then it has long arrived, so nothing waits, and which solve switches is a function
-					// of the step sequence, not of when the host happened to look (the unsynchronised read made launch sequences,
-					// step times and kernel statistics vary from run to run around the threshold)
-					if ((gen & 3u) == 2u && m->fz_active_pending) {
-						FX_HIP(hipEventSynchronize(m->fz_active_ev));
-						m->fz_active_pending = false;
-						const uint32_t active = *(volatile uint32_t*)m->fz_active_host, tiles = (uint32_t)jacobi_freeze_tiles(m->g);
-						// how many strip launches, with hysteresis.  Four levels per launch (k_freeze_strip4o behind a one-copy dense sweep): one
-						// launch pays from a fifth of the tiles (256^3 plume: frame ~70, 0.600 -> 0.585 ms per step; at a half, frame 110: 0.747 ->
-						// 0.671), a second one from two thirds (frame ~140; frame 190: 0.790 -> 0.759).  Three levels per launch
-						// (k_freeze_strip3, 30 us per level): one launch from half of the tiles.
-						int n = m->fz_dense_n;
-						if (strip_four) {
-							if (n == 0 && 5u * active >= tiles) n = 1;
-							else if (n >= 1 && 6u * active < tiles) n = 0;
-							if (n == 1 && 16u * active >= 11u * tiles) n = 2;
-							else if (n == 2 && 8u * active < 5u * tiles) n = 1;
-						} else {
-							if (n == 0 && 2u * active >= tiles) n = 1;
-							else if (n >= 1 && 5u * active < 2u * tiles) n = 0;
-							if (n > 1) n = 1;
-						}
-						m->fz_dense_n = n;
-					}
-					strip_want = m->fz_dense_n * (strip_four ? 4 : 3);
-					count_marks_now = (gen & 3u) == 0u;
-				}
-			}
+		// the strip launches in use follow the count k_count_marks put into a host-visible word behind an earlier solve's dense sweep;
+		// decided HERE because the dense sweep itself depends on what follows it
+		int forced;
+		const int width = freeze_strip_width(m->g, multi, m->fz_mask[2] != nullptr, &forced);
+		const bool adaptive = width && forced < 0 && m->fz_active_dev;      // the count of relaxing tiles decides how many strip launches
+		const FreezeCadence cadence = freeze_cadence(gen);
+		if (adaptive && cadence.take_over && m->fz_active_pending) {
+			FX_HIP(hipEventSynchronize(m->fz_active_ev));
+			m->fz_active_pending = false;
+			m->fz_dense_n = freeze_strip_hysteresis(m->fz_dense_n, *(volatile uint32_t*)m->fz_active_host, (uint32_t)jacobi_freeze_tiles(m->g), width == 4);
 		}
-		const bool one_copy = strip_want >= 3 && iters - 1 > 3 && FX_KNOB_INT("FREEZE_DENSE_ONE", 1);   // a strip launch follows (the loop below)
+		launches = freeze_plan(m->g, iters, multi, m->fz_mask[2] != nullptr, adaptive ? m->fz_dense_n : 0, plan);
+		if (!launches) return FX_E_STATE;                               // (takes_sparse_solver admits no solve whose launches outnumber the counters)
+		const bool one_copy = plan[0].kind == FZ_DENSE_ONE;
 		mk[i].reset(new ScopedMark(m, ms, MK_JACOBI));
-		FX_HIP(launch_freeze_dense(r.v, r.src + r.off, m->b + r.off, r.a + r.off, one_copy ? nullptr : r.d + r.off, r.ma + moff, one_copy ? nullptr : r.md + moff, r.w, ms,
+		FX_HIP(launch_freeze_dense(r.v, r.src + r.off, m->b + r.off, r.a + r.off, one_copy ? nullptr : r.d + r.off, r.ma + r.moff, one_copy ? nullptr : r.md + r.moff, r.w, ms,
 			fuse ? (const char*)m->vel[1] + r.off * es : nullptr, m->half, r.own0, m->g.nz, m->g.cells_local()));
 		mk[i]->launches = 1; mk[i]->sweeps = 1;
 		if (multi || iters == 1) mk[i].reset(); else mk[i]->split(MK_JACOBI_TAIL);
+		if (adaptive && cadence.count) {                                   // (single domain: no exchange stands between the dense sweep and this)
+			FX_HIP(launch_count_marks(r.w.tile_mark, gen, jacobi_freeze_tiles(m->g), m->fz_active_dev, ms));
+			if (!m->fz_active_ev) FX_HIP(hipEventCreateWithFlags(&m->fz_active_ev, hipEventDisableTiming));
+			FX_HIP(hipEventRecord(m->fz_active_ev, ms));
+			m->fz_active_pending = true;
+		}
 	}
 	auto exchange = [&](bool with_b) -> int {
 		if (!multi) return FX_OK;
@@ -465,54 +437,27 @@ static int jacobi_freeze(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, u
 	};
 	int rc = exchange(true);                                            // level 1 and the divergence across the faces
 	if (rc) return rc;
-	const int T = jacobi_freeze_levels_per_launch();
-	int level = 1, n = 0;
-	uint32_t left = iters - 1, flag_tag = 0;
-	// While most tiles still relax the tile launches are dense sweeps in all but name (43 us per level at 256^3, a cone five times the
-	// core per tile): the levels right behind the dense sweep go through a masked strip pipeline instead -- k_freeze_strip4o
-	// (fx_jacobi_strip4.hip: four levels per launch for every cell, 22 us per level) or k_freeze_strip3 (fx_jacobi_stripm.hip: three, 30 us
-	// per level) -- which leaves its last level in two of the three pressure buffers -- they rotate -- and the tile marks for the first
-	// tile launch.  Single domain, X = 256; how many levels was decided in front of the dense sweep.
-	if (!multi && jacobi_freeze_strip_supported(M[0]->g) && M[0]->fz_mask[2]) {
-		fx_ctx* m = M[0];
-		Run& r = R[0];
-		int want = strip_want;
-		const bool strip4 = strip_four;
-		if (count_marks_now) {
-			FX_HIP(launch_count_marks(r.w.tile_mark, r.w.gen, jacobi_freeze_tiles(m->g), m->fz_active_dev, CS(m, s)));
-			if (!m->fz_active_ev) FX_HIP(hipEventCreateWithFlags(&m->fz_active_ev, hipEventDisableTiming));
-			FX_HIP(hipEventRecord(m->fz_active_ev, CS(m, s)));
-			m->fz_active_pending = true;
-		}
-		// a launch takes FOUR levels where the octet serves the grid (k_freeze_strip4o, fx_jacobi_strip4.hip; FREEZE_STRIP4=0: never), else three
-		const bool four = strip4;
-		for (int k = 0; want >= 3 && left > 3; ++k) {
-			DeviceGuard dg(m->device);
-			const int lv = four && want >= 4 && left > 4 ? 4 : 3;
-			flag_tag = r.w.gen | ((uint32_t)(k + 1) << 24);
-			if (lv == 4) { FX_HIP(launch_freeze_strip4(r.v, r.a, m->b, r.d, r.src, r.ma, r.md, r.mx, r.w.tile_mark, flag_tag, r.stat, r.stat_hi, level, CS(m, s))); }
-			else { FX_HIP(launch_freeze_strip3(r.v, r.a, m->b, r.d, r.src, r.ma, r.md, r.mx, r.w.tile_mark, flag_tag, r.stat, r.stat_hi, level, CS(m, s))); }
-			if (mk[0]) { mk[0]->launches += 1; mk[0]->sweeps += (uint64_t)lv; }
-			m->acc.freeze_strip_launches += 1;                                  // (counted like the solves: with or without the timing marks)
-			float* na = r.d; r.d = r.src; r.src = r.a; r.a = na;                  // level + lv now sits in (a, d); the buffer it was read from is the spare
-			uint8_t* nm = r.md; r.md = r.mx; r.mx = r.ma; r.ma = nm;
-			level += lv; left -= (uint32_t)lv; want -= lv;
-		}
-	}
-	for (; left > 0; ++n) {
-		const int t = (int)std::min<uint32_t>((uint32_t)T, left);
+	uint32_t flag_tag = 0;                                              // what the last strip launch wrote into the tile marks, for the first tile launch
+	for (int j = 1, n = 0; j < launches; ++j) {
+		const FreezeLaunch& l = plan[j];
+		const bool strip = l.kind == FZ_STRIP;
+		if (strip) flag_tag = R[0].w.gen | ((uint32_t)j << 24);
 		for (size_t i = 0; i < M.size(); ++i) {
 			fx_ctx* m = M[i];
 			Run& r = R[i];
 			DeviceGuard dg(m->device);
-			const size_t moff = r.off / m->g.plane() * (size_t)((m->g.X + 3) / 4) * m->g.Y;
 			if (!mk[i]) mk[i].reset(new ScopedMark(m, CS(m, s), MK_JACOBI_TAIL));
-			FX_HIP(launch_freeze_tiles(r.v, r.a + r.off, m->b + r.off, r.d + r.off, r.ma + moff, r.md + moff, r.w, n, t, level, r.stat, r.stat_hi, CS(m, s), r.own0, m->g.nz, n == 0 ? flag_tag : 0u));
-			mk[i]->launches += 1; mk[i]->sweeps += (uint64_t)t;
+			if (strip)                                                      // reads (a, ma), leaves level base + levels in (d, src) and (md, mx)
+				FX_HIP((l.levels == 4 ? launch_freeze_strip4 : launch_freeze_strip3)(r.v, r.a, m->b, r.d, r.src, r.ma, r.md, r.mx, r.w.tile_mark, flag_tag, r.stat, r.stat_hi, l.base, CS(m, s)));
+			else
+				FX_HIP(launch_freeze_tiles(r.v, r.a + r.off, m->b + r.off, r.d + r.off, r.ma + r.moff, r.md + r.moff, r.w, n, l.levels, l.base, r.stat, r.stat_hi, CS(m, s), r.own0, m->g.nz, n == 0 ? flag_tag : 0u));
+			m->acc.freeze_strip_launches += strip;                          // (counted like the solves: with or without the timing marks)
+			mk[i]->launches += 1; mk[i]->sweeps += (uint64_t)l.levels;
 			if (multi) mk[i].reset();
-			std::swap(r.a, r.d); std::swap(r.ma, r.md);
+			freeze_rotate(r.a, r.d, r.src, strip);
+			freeze_rotate(r.ma, r.md, r.mx, strip);
 		}
-		left -= (uint32_t)t; level += t;
+		if (!strip) ++n;
 		if ((rc = exchange(false))) return rc;                          // the levels just made, kFreezeHalo planes deep (the last one serves the projection)
 	}
 	mk.clear();

@@ -2,6 +2,7 @@
 sweeps, per-cell early-out at |dx| < 1e-3) on the sparse solver of fx_jacobi_freeze.hip: a dense first sweep + launches of <= 4
 levels over the 32 x 8 x 8 tiles that still relax.  Bar: BIT-EXACT against the oracle's lock-step replay (orc_jacobi mode 1), the same
 number of executed sweeps, and bit-identical to the one-sweep-per-launch kernel with the byte mask (k_jacobi_generic)."""
+import json
 import os
 
 import numpy as np
@@ -174,7 +175,7 @@ def test_masked_strip_levels_equal_oracle(dims, iters, levels, strip4, knobs):
     got, t = solve(dims, p, b, iters)
     assert np.array_equal(got, want)
     assert (t.freeze_solves, t.freeze_sweeps) == (1, k)
-    launches, left, w = 0, iters - 1, levels                 # fx_schedule.cpp jacobi_freeze: fours while four levels are wanted and left behind them
+    launches, left, w = 0, iters - 1, levels                 # fx_jacobi_plan.cpp freeze_plan, restated: fours while four levels are wanted and left behind them
     while w >= 3 and left > 3:
         lv = 4 if strip4 and w >= 4 and left > 4 else 3
         launches, left, w = launches + 1, left - lv, w - lv
@@ -225,3 +226,28 @@ def test_masked_strip_levels_change_no_step(storage, knobs):
         for u, v in zip(ref[:3], got[:3]):
             assert np.array_equal(u.view(np.uint8), v.view(np.uint8)), levels
         assert ref[3:] == got[3:], levels
+
+
+def test_adaptive_strip_launches_follow_the_recorded_sequence():
+    """whole steps at the library's own settings (no switch set: FREEZE_DENSE_LEVELS = -1), where the count of relaxing tiles decides how many
+    masked strip launches a solve takes: every fourth solve counts, the solve two later takes the count over through the hysteresis
+    (fx_jacobi_plan.cpp: freeze_cadence, freeze_strip_hysteresis, freeze_plan).  Step by step the strip launches, all launches and the levels
+    they carry are those the commit before the planner ran (tests/golden/freeze_plan.json "adaptive": recorded on that commit on an MI355X),
+    and the recording holds solves without a strip launch and solves with one: the hysteresis is crossed"""
+    rec = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "freeze_plan.json")))["adaptive"]
+    assert (rec["dims"], rec["iters"]) == ([256, 256, 48], 64) and len(rec["sequence"]) == rec["steps"]
+    strips = [s[0] for s in rec["sequence"]]
+    assert 0 in strips and max(strips) >= 1
+    f = make(tuple(rec["dims"]), jacobi_iters=rec["iters"], jacobi_mode="faithful", storage=rec["storage"])
+    f.timing_enable(True)
+    dt = f32(f.default_time_step() * rec["time_step_factor"])
+    got = []
+    for k in range(rec["steps"]):
+        f.UpdateFrame(dt, k % 3)
+        f.Simulate(k % 3)
+        f.Synchronize()
+        t = f.timing_read(True)
+        got.append([t.freeze_strip_launches, t.jacobi_launches, t.jacobi_sweeps])
+    f.Release()
+    print(got)
+    assert got == rec["sequence"]       # [freeze_strip_launches, jacobi_launches, jacobi_sweeps] of each step
