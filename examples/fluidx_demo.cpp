@@ -3,6 +3,7 @@
 // (:465,489-490), minus the window.  Build (after `python -m fluidx12_amd.build`):
 //   hipcc -std=c++17 examples/fluidx_demo.cpp -o fluidx_demo -Lfluidx12_amd -lfluidx_hip -Wl,-rpath,$PWD/fluidx12_amd
 // Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
+//        [-emitter CX CY CZ R]... [-noimpulse]     (smoke sources, fx_set_emitters: texture space [0,1]^3, with the built-in's colour and lift; -noimpulse: without the reference's own source)
 //        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
@@ -93,6 +94,8 @@ int main(int argc, char** argv)
 	const char* resume = nullptr;                       // not in the reference: continue from / leave behind a state file
 	const char* checkpoint = nullptr;
 	float vorticity = 0.0f;                             // not in the reference: strength of the vorticity confinement, 0 = off
+	std::vector<fx_emitter> emitters;                   // not in the reference: its only source is the impulse inside its advection
+	bool noImpulse = false;
 	bool lightSet = false, pointLight = false, colorSet = false, ambientSet = false;   // not in the reference: its light is three constants (Fluid.cpp:169-173)
 	float lightPos[3] = { 75.0f, 75.0f, -75.0f }, lightColor[4] = {}, ambient[4] = {};
 	for (int i = 1; i < argc; ++i) {
@@ -105,6 +108,14 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-resume") && i + 1 < argc) resume = argv[++i];
 		else if (!std::strcmp(argv[i], "-checkpoint") && i + 1 < argc) checkpoint = argv[++i];
 		else if (!std::strcmp(argv[i], "-vorticity") && i + 1 < argc) vorticity = (float)atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "-emitter") && i + 4 < argc) {
+			fx_emitter e = {};
+			e.struct_size = sizeof e;
+			for (float& v : e.center) v = (float)atof(argv[++i]);
+			e.radius = (float)atof(argv[++i]);
+			emitters.push_back(e);
+		}
+		else if (!std::strcmp(argv[i], "-noimpulse")) noImpulse = true;
 		else if (!std::strcmp(argv[i], "-light") && i + 3 < argc) { for (float& v : lightPos) v = (float)atof(argv[++i]); lightSet = true; }
 		else if (!std::strcmp(argv[i], "-pointLight")) { pointLight = true; lightSet = true; }
 		else if (!std::strcmp(argv[i], "-lightColor") && i + 4 < argc) { for (float& v : lightColor) v = (float)atof(argv[++i]); colorSet = lightSet = true; }
@@ -117,6 +128,14 @@ int main(int argc, char** argv)
 	}
 	fluid.SetMaxSamples(maxRay, maxLight);
 	if (vorticity != 0.0f && !fluid.SetVorticityConfinement(vorticity)) { std::fprintf(stderr, "-vorticity %g: %s\n", vorticity, fx_error_string(fluid.LastStatus())); return 1; }
+	for (fx_emitter& e : emitters) {                    // the built-in's colour, lift and swirl (Impulse.hlsli; 2-D: CSAdvect.hlsl's 48)
+		const float rate[4] = { 8.0f, 16.0f, 40.0f, 40.0f };
+		std::memcpy(e.color_rate, rate, sizeof rate);
+		e.force[1] = grid.z > 1 ? 192.0f : 48.0f;
+		e.swirl = 200.0f;
+	}
+	if (!emitters.empty() && !fluid.SetEmitters(emitters)) { std::fprintf(stderr, "-emitter: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	if (noImpulse && !fluid.SetImpulse(false)) { std::fprintf(stderr, "-noimpulse: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (lightSet && grid.z <= 1) std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: a 2-D grid has no light; ignored\n");
 	if (lightSet && grid.z > 1 && !fluid.SetLight(lightPos, pointLight, colorSet ? lightColor : nullptr, ambientSet ? ambient : nullptr)) {
 		std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: %s\n", fx_error_string(fluid.LastStatus()));

@@ -23,6 +23,7 @@ ABI_VERSION = 7                      # FX_ABI_VERSION of include/fluidx_hip.h
  FIELD_LIGHTMAP, FIELD_CUBEMAP, FIELD_TARGET, FIELD_TARGET_FLOAT, FIELD_CUBE_DEPTH) = range(11)
 DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is device memory, read in place
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
+MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
 
 
 class Desc(C.Structure):
@@ -42,6 +43,11 @@ class FrameInfo(C.Structure):
 class Light(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("position", C.c_float * 3), ("color", C.c_float * 4),
                 ("ambient", C.c_float * 4)]
+
+
+class Emitter(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_float),
+                ("color_rate", C.c_float * 4), ("force", C.c_float * 3), ("swirl", C.c_float)]
 
 
 class Timing(C.Structure):
@@ -83,6 +89,10 @@ SYMBOLS = {
     "fx_project": (C.c_int, [_vp, _vp]),
     "fx_set_vorticity_confinement": (C.c_int, [_vp, C.c_float]),
     "fx_confine_vorticity": (C.c_int, [_vp, _vp]),
+    "fx_set_emitters": (C.c_int, [_vp, C.POINTER(Emitter), C.c_uint32]),
+    "fx_get_emitters": (C.c_int, [_vp, C.POINTER(Emitter), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fx_set_impulse": (C.c_int, [_vp, C.c_int]),
+    "fx_emit": (C.c_int, [_vp, _vp]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),

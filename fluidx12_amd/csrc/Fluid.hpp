@@ -113,6 +113,22 @@ public:
 	// not in the reference: vorticity confinement between advection and divergence (fx_set_vorticity_confinement); 0 = off (default)
 	bool SetVorticityConfinement(float epsilon) { m_status = fx_set_vorticity_confinement(m_ctx, epsilon); return m_status == FX_OK; }
 
+	// not in the reference (its only source is the impulse compiled into its advection): smoke emitters applied behind every advection
+	// (fx_set_emitters; count 0 = none, the default), and the switch of that built-in impulse (fx_set_impulse; default on)
+	bool SetEmitters(const fx_emitter* list, uint32_t count) { m_status = fx_set_emitters(m_ctx, list, count); return m_status == FX_OK; }
+	bool SetEmitters(const std::vector<fx_emitter>& list) { return SetEmitters(list.data(), (uint32_t)list.size()); }
+	bool GetEmitters(std::vector<fx_emitter>& out)
+	{
+		uint32_t n = 0;
+		out.resize(FX_MAX_EMITTERS);
+		m_status = fx_get_emitters(m_ctx, out.data(), FX_MAX_EMITTERS, &n);
+		out.resize(m_status == FX_OK ? n : 0);
+		return m_status == FX_OK;
+	}
+	bool SetImpulse(bool enabled) { m_status = fx_set_impulse(m_ctx, enabled ? 1 : 0); return m_status == FX_OK; }
+	// the emitter stage alone (fx_emit), beside the stage calls of the C interface
+	bool Emit(void* stream = nullptr) { m_status = fx_emit(m_ctx, stream); return m_status == FX_OK; }
+
 	// not in the reference (its state dies with the window): whole-grid state files, see fx_checkpoint_save
 	bool SaveCheckpoint(const char* path) { m_status = fx_checkpoint_save(m_ctx, path); return m_status == FX_OK; }
 	bool LoadCheckpoint(const char* path) { m_status = fx_checkpoint_load(m_ctx, path); return m_status == FX_OK; }

@@ -196,8 +196,8 @@ __device__ __forceinline__ void advect_finish(const SimParams& sp, float (&u)[3]
 	uint32_t id, uint32_t stride, void* __restrict__ vel_out, void* __restrict__ col_out, float* __restrict__ alpha_out)
 {
 	// ---- impulse (CSAdvect.hlsl:59-68).  exp2(ex) >= e^-4 needs ex >= -5.77: a wave whose lanes are all far below that
-	// skips the transcendental; the decision itself still uses the computed basis, exactly as before
-	if (__builtin_amdgcn_ballot_w64(ex > -6.5f) != 0) {
+	// skips the transcendental; the decision itself still uses the computed basis, exactly as before.  fx_set_impulse(0): no lane asks for it
+	if (__builtin_amdgcn_ballot_w64(sp.impulse && ex > -6.5f) != 0) {
 		const float basis = exp2f(ex);
 		if (basis >= 0.0183156393f) {
 			float Fx, Fy, Fz;

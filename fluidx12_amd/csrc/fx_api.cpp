@@ -415,6 +415,50 @@ int fx_confine_vorticity(fx_ctx* ctx, void* stream)
 	return confine_phase(ctx, pick_stream(ctx, stream));
 }
 
+int fx_set_emitters(fx_ctx* ctx, const fx_emitter* list, uint32_t count)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;          // (before every other test: the header promises it for all four calls)
+	if (count > FX_MAX_EMITTERS || (count && !list)) return FX_E_INVALID;
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: the colour halos leave right behind the advection
+	for (uint32_t k = 0; k < count; ++k) {
+		const fx_emitter& e = list[k];
+		if (e.struct_size != sizeof(fx_emitter) || e.flags != 0) return FX_E_INVALID;
+		if (!std::isfinite(e.radius) || !(e.radius > 0.0f) || !std::isfinite(e.swirl)) return FX_E_INVALID;
+		for (int a = 0; a < 3; ++a) if (!std::isfinite(e.center[a]) || !std::isfinite(e.force[a])) return FX_E_INVALID;
+		for (int a = 0; a < 4; ++a) if (!std::isfinite(e.color_rate[a]) || e.color_rate[a] < 0.0f) return FX_E_INVALID;
+	}
+	ctx->emitters.assign(list, list + count);
+	return FX_OK;
+}
+
+int fx_get_emitters(fx_ctx* ctx, fx_emitter* out, uint32_t capacity, uint32_t* count)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (!count || (capacity && !out)) return FX_E_INVALID;
+	*count = (uint32_t)ctx->emitters.size();
+	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->emitters[k];
+	return FX_OK;
+}
+
+int fx_set_impulse(fx_ctx* ctx, int enabled)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (!enabled && (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1)) return FX_E_INVALID;   // on the emitters' footing: without it a slab rank has no source
+	ctx->impulse_on = enabled != 0;
+	return FX_OK;
+}
+
+int fx_emit(fx_ctx* ctx, void* stream)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	return emit_phase(ctx, pick_stream(ctx, stream));
+}
+
 int fx_divergence(fx_ctx* ctx, void* stream)
 {
 	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;

@@ -60,6 +60,9 @@ struct fx_ctx {
 	float depth_zn, depth_zf;
 	// vorticity confinement (fx_set_vorticity_confinement; configuration like the scene depth: kept across fx_update_frame, never checkpointed or digested)
 	float vort_eps = 0.0f;          // 0 = off
+	// the smoke sources (fx_set_emitters / fx_set_impulse; configuration on the same terms)
+	std::vector<fx_emitter> emitters;   // applied by k_emit behind every advection, in this order; empty = none (default)
+	bool impulse_on = true;         // the reference's built-in impulse inside the advection kernels
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

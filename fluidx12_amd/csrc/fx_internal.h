@@ -52,6 +52,7 @@ struct SimParams {
 	float dt;
 	int address;           // fx_address
 	int is3d;
+	int impulse = 1;       // the reference's built-in source (CSAdvect.hlsl:59-68) is on; 0: fx_set_impulse switched it off
 };
 
 // ---- simulation launchers (fx_sim.hip); `half_store` selects __half storage of velocity/colour
@@ -72,6 +73,15 @@ size_t advect_far_words(const Geom& g, int nzp);
 // vorticity confinement of a whole-grid velocity (fx_vorticity.hip), vel_in -> vel_out (never in place: the cell stencil has radius 2);
 // hipErrorNotSupported for a slab geometry
 hipError_t launch_confine_vorticity(const Geom& g, int half_store, const void* vel_in, void* vel_out, float eps, float dt, hipStream_t s);
+// the settable emitters (fx_emit.hip), in place on a whole-grid velocity and colour; hipErrorNotSupported for a slab geometry.
+// EmitArgs is what the kernel gets: the emitters whose clipped bounding box [lo, hi) holds a cell, in list order, and the 64 x 4 x 1 tiles
+// over the union of the boxes (first tile at (x0, y0, z0), on the grid's own 64 x 4 raster).  emit_plan (fx_emit_plan.cpp) fills it -> workgroups to launch
+// (0: nothing, below 0: too many); host code, no device needed.  alpha: the render's side volume when it holds this colour field's alpha, else null
+const int kEmitTileX = 64, kEmitTileY = 4;
+struct EmitBall { float c[3], rr, rate[4], force[3], swirl; int lo[3], hi[3]; };
+struct EmitArgs { int n, x0, y0, z0, tiles_x, tiles_y, tiles_z; EmitBall e[FX_MAX_EMITTERS]; };
+int emit_plan(const Geom& g, const fx_emitter* list, int count, EmitArgs* out);
+hipError_t launch_emit(const Geom& g, int half_store, void* vel, void* col, float* alpha, const fx_emitter* list, int count, float dt, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
 // one lock-step sweep p_in -> p_out on planes [z_begin, z_end); frozen may be null
 hipError_t launch_jacobi_sweep(const Geom& g, const float* p_in, const float* b, float* p_out, uint8_t* frozen,

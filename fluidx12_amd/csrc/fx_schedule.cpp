@@ -99,7 +99,7 @@ int advect_range(fx_ctx* ctx, hipStream_t s, Range r, bool own_only)
 {
 	if (r.hi <= r.lo) return FX_OK;
 	DeviceGuard dg(ctx->device);
-	const SimParams sp{ ctx->time_step, (int)ctx->desc.advect_address, ctx->g.Zg > 1 ? 1 : 0 };
+	const SimParams sp{ ctx->time_step, (int)ctx->desc.advect_address, ctx->g.Zg > 1 ? 1 : 0, ctx->impulse_on ? 1 : 0 };
 	const int par = ctx->frame_parity;
 	Geom g = ctx->g;
 	// only halo_advect planes per side were refreshed by EX_ADVECT_IN; the allocation may be wider (max with halo_jacobi), and
@@ -294,6 +294,20 @@ int confine_phase(fx_ctx* ctx, hipStream_t s)
 	ScopedMark mk(ctx, s, MK_ADVECT);
 	FX_HIP(launch_confine_vorticity(ctx->g, ctx->half, ctx->vel[1], ctx->vel[0], ctx->vort_eps, ctx->time_step, s));
 	std::swap(ctx->vel[0], ctx->vel[1]);
+	return FX_OK;
+}
+
+// The settable emitters (fx_emit.hip) add to the advected velocity and colour in place, in front of the confinement and of the divergence
+// (the sparse solver's fused one included: it reads velocity[1] behind this launch), booked with the advection like the confinement.
+// When this step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well.
+int emit_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (ctx->emitters.empty() || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	const int par = ctx->frame_parity;
+	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
+	FX_HIP(launch_emit(ctx->g, ctx->half, ctx->vel[1], ctx->col[par], alpha, ctx->emitters.data(), (int)ctx->emitters.size(), ctx->time_step, s));
 	return FX_OK;
 }
 
@@ -618,7 +632,7 @@ int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t it
 int project_phase(fx_ctx* ctx, hipStream_t s)
 {
 	DeviceGuard dg(ctx->device);
-	const SimParams sp{ ctx->time_step, (int)ctx->desc.advect_address, ctx->g.Zg > 1 ? 1 : 0 };
+	const SimParams sp{ ctx->time_step, (int)ctx->desc.advect_address, ctx->g.Zg > 1 ? 1 : 0, 1 };
 	ScopedMark mk(ctx, s, MK_PROJECT);
 	const Range r = owned(ctx);
 	int* rec = multi_rank(ctx) ? ctx->step_rec : nullptr;           // slab ranks: the projection also measures the next advection's need
@@ -644,6 +658,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		for (fx_ctx* m : M) m->col_halo_buf = (int)m->frame_parity;
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
+		for (fx_ctx* m : M) if ((rc = emit_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with emitters set only)
 		for (fx_ctx* m : M) if ((rc = confine_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with epsilon > 0 only)
 		const ExchSpec uz{ EX_UZ1, 1, 0 };
 		if ((rc = do_exchange(ctx, M, &uz, 1, ON_COMPUTE, s))) return rc;

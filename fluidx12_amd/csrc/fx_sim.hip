@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void k_advect(const Geom g, const SimParams sp
 #undef FX_TRI
 	}
 
-	if (basis >= 0.0183156393f) {                                            // :60
+	if (sp.impulse && basis >= 0.0183156393f) {                              // :60 (fx_set_impulse: a uniform flag)
 		u[0] = fmaf(Fx, dt, u[0]); u[1] = fmaf(Fy, dt, u[1]); u[2] = fmaf(Fz, dt, u[2]);   // :66
 		const float bdt = basis * dt;
 		c[0] = saturatef(fmaf(bdt, 8.0f, c[0]));                             // :67, g_impulse = (.2,.4,1,1)*40
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256) void k_advect_fast(const Geom g, const SimPara
 		c[0] = FX_TRI(x); c[1] = FX_TRI(y); c[2] = FX_TRI(z); c[3] = FX_TRI(w);
 #undef FX_TRI
 	}
-	if (basis >= 0.0183156393f) {
+	if (sp.impulse && basis >= 0.0183156393f) {
 		u[0] = fmaf(Fx, dt, u[0]); u[1] = fmaf(Fy, dt, u[1]); u[2] = fmaf(Fz, dt, u[2]);
 		const float bdt = basis * dt;
 		c[0] = saturatef(fmaf(bdt, 8.0f, c[0]));

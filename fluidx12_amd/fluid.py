@@ -264,6 +264,46 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_confine_vorticity(self._ctx, stream), "ConfineVorticity")
 
+    def SetEmitters(self, emitters):
+        """the smoke sources applied behind every advection (fx_set_emitters): a sequence of dicts (or capi.Emitter) with "center" (x, y, z) and
+        "radius" in the simulation's texture space [0, 1]^3, and optionally "color_rate" (r, g, b, a per unit time; default the built-in's
+        8, 16, 40, 40), "force" (default the built-in's lift: (0, 192, 0), 2-D grids (0, 48, 0)) and "swirl" (default 200; ignored in 2-D).
+        None or () = none (default).  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid contexts only."""
+        self._need()
+        items = list(emitters or ())
+        arr = (capi.Emitter * max(len(items), 1))()
+        is3d = self.grid[2] > 1
+        for k, e in enumerate(items):
+            if isinstance(e, capi.Emitter):
+                arr[k] = e
+                continue
+            arr[k].struct_size, arr[k].flags = C.sizeof(capi.Emitter), int(e.get("flags", 0))
+            arr[k].center = (C.c_float * 3)(*[float(v) for v in e["center"]])
+            arr[k].radius = float(e["radius"])
+            arr[k].color_rate = (C.c_float * 4)(*[float(v) for v in e.get("color_rate", (8.0, 16.0, 40.0, 40.0))])
+            arr[k].force = (C.c_float * 3)(*[float(v) for v in e.get("force", (0.0, 192.0 if is3d else 48.0, 0.0))])
+            arr[k].swirl = float(e.get("swirl", 200.0))
+        capi.check(self._lib.fx_set_emitters(self._ctx, arr if items else None, len(items)), "SetEmitters")
+
+    def GetEmitters(self):
+        """the list in force (fx_get_emitters), as dicts with the keys SetEmitters takes"""
+        self._need()
+        n = C.c_uint32(0)
+        arr = (capi.Emitter * capi.MAX_EMITTERS)()
+        capi.check(self._lib.fx_get_emitters(self._ctx, arr, capi.MAX_EMITTERS, C.byref(n)), "GetEmitters")
+        return [{"center": tuple(e.center), "radius": e.radius, "color_rate": tuple(e.color_rate), "force": tuple(e.force), "swirl": e.swirl,
+                 "flags": e.flags} for e in arr[:n.value]]
+
+    def SetImpulse(self, enabled):
+        """the reference's built-in source inside the advection (fx_set_impulse); default on.  Off: the emitters are the only sources"""
+        self._need()
+        capi.check(self._lib.fx_set_impulse(self._ctx, 1 if enabled else 0), "SetImpulse")
+
+    def Emit(self, stream=None):
+        """the emitter stage alone, in place on VELOCITY1 and COLOR (fx_emit); Advect does not include it"""
+        self._need()
+        capi.check(self._lib.fx_emit(self._ctx, stream), "Emit")
+
     def Divergence(self, stream=None):
         capi.check(self._lib.fx_divergence(self._ctx, stream), "Divergence")
 

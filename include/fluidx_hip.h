@@ -289,6 +289,49 @@ int fx_project(fx_ctx* ctx, void* stream);
 int fx_set_vorticity_confinement(fx_ctx* ctx, float epsilon);
 int fx_confine_vorticity(fx_ctx* ctx, void* stream);
 
+/* Smoke sources (no reference counterpart: the reference's only source is the impulse compiled into its advection, CSAdvect.hlsl:59-68 /
+ * Impulse.hlsli -- a Gaussian ball at (0.5, 0.1, 0.5), radius 1/16 (2-D: 1/32), colour rate (8, 16, 40, 40), lift 192 (2-D: 48), swirl 200).
+ * fx_set_emitters gives the context a list of such balls with every constant an argument; with a non-empty list fx_simulate runs one more
+ * pass (one launch, over the cells the balls cover, not over the grid) between the advection and the vorticity confinement / divergence,
+ * in place on VELOCITY1 and COLOR.  Per cell (x, y, z) and emitter e, in list order, fp32 in the built-in's own operation order:
+ *   p = ((x + .5) / X, (y + .5) / Y, (z + .5) / Z)      d = p - e.center (2-D grids: dz = 0)      d2 = fma(dz, dz, fma(dy, dy, dx * dx))
+ *   basis = exp2(((d2 * -4) / (radius * radius)) * 1.44269502)
+ *   if (basis >= e^-4) {      -- i.e. within `radius` of the centre
+ *       F = 3-D: (fma(basis, fx, dz * -swirl), fma(basis, fy, 0), fma(basis, fz, dx * swirl))      2-D: (basis * fx, basis * fy, 0)
+ *       u = fma(F, dt, u)      c[i] = saturate(fma(basis * dt, color_rate[i], c[i]))
+ *   }
+ * (tests/emitter_ref.py restates it in numpy.)  An emitter with the built-in's constants forms the built-in's basis bit for bit.  One
+ * documented difference: the built-in adds in front of the step's attenuation max(1 - 0.2 dt, 0), an emitter behind it -- what an emitter
+ * injects is not attenuated in the step that injects it.  fp16 storage widens on load and rounds each stored value once (RNE) behind the
+ * last emitter; a cell in no emitter's support keeps its bits.  The list travels with the launch (no device memory, no copy, no
+ * synchronisation): a moving source is a new fx_set_emitters per frame and costs nothing on the device.
+ * fx_set_emitters: count 0 (list may be NULL) = none, the default: every call behaves exactly as without this function.  FX_E_INVALID,
+ * the previous list staying in force, for a wrong struct_size, count > FX_MAX_EMITTERS, a non-finite member, radius <= 0, a negative
+ * color_rate and unknown flag bits.  fx_get_emitters: the list in force -- *count gets its length, out (may be NULL with capacity 0) the
+ * first min(capacity, length) entries.
+ * fx_set_impulse: 0 switches the reference's built-in source off (a uniform flag in the advection kernels), so that the emitters are the
+ * only sources; default 1.
+ * Configuration like the vorticity confinement: per context, kept across fx_update_frame, not checkpointed (set it again after
+ * fx_checkpoint_load), not part of fx_field_digest.  fx_set_emitters and fx_set_impulse(0) return FX_E_INVALID for a context that owns
+ * fewer planes than the grid (slab ranks, over RCCL or in-process groups, on the same footing as the confinement: the overlapped schedule
+ * sends the colour halos right behind the advection, and ordering an in-place pass against that exchange is work of its own); all four
+ * calls return FX_E_STATE for FX_FLAG_RENDER_ONLY contexts.
+ * fx_emit: the stage alone, beside fx_advect / fx_confine_vorticity (fx_advect does not include it), with the time step of the last
+ * fx_update_frame; nothing (FX_OK) with an empty list or dt <= 0.  Timing: booked into fx_timing.advect_ms. */
+#define FX_MAX_EMITTERS 16u
+typedef struct fx_emitter {
+	uint32_t struct_size, flags;   /* flags: 0 (unknown bits: FX_E_INVALID) */
+	float center[3];               /* the simulation's texture space [0,1]^3: cell (x,y,z) sits at ((x+.5)/X, (y+.5)/Y, (z+.5)/Z); may lie outside the volume */
+	float radius;                  /* same space; support = cells with basis >= e^-4, i.e. within `radius` of the centre */
+	float color_rate[4];           /* rgba added per unit time at the centre (built-in: 8, 16, 40, 40); >= 0 */
+	float force[3];                /* acceleration at the centre, scaled by basis (built-in: 0, 192, 0; 2-D: 0, 48, 0) */
+	float swirl;                   /* adds swirl * (-dz, 0, dx), NOT scaled by basis, inside the support (built-in: 200; ignored on 2-D grids) */
+} fx_emitter;
+int fx_set_emitters(fx_ctx* ctx, const fx_emitter* list, uint32_t count);
+int fx_get_emitters(fx_ctx* ctx, fx_emitter* out, uint32_t capacity, uint32_t* count);
+int fx_set_impulse(fx_ctx* ctx, int enabled);
+int fx_emit(fx_ctx* ctx, void* stream);
+
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
 int fx_sh_transform(fx_ctx* ctx, const float* cube, uint32_t n, float* out27);
