@@ -7,6 +7,17 @@
 using namespace fx;
 using namespace fxh;
 
+namespace fx {
+// 64-bit sums: z_begin + z_count cannot wrap past the check (5 + 0xFFFFFFFF would pass a 32-bit one)
+bool digest_range_ok(const Geom& g, uint32_t z_begin, uint32_t z_count)
+{
+	if (!z_count) return true;                                      // all owned planes
+	if (g.nz < 0 || z_count > (uint32_t)g.nz) return false;
+	const int64_t first = (int64_t)z_begin, end = first + (int64_t)z_count;
+	return first >= (int64_t)g.z0 && end <= (int64_t)g.z0 + (int64_t)g.nz;
+}
+}  // namespace fx
+
 namespace fxh {
 
 size_t ev_record(fx_ctx* c, hipStream_t s)
@@ -402,8 +413,8 @@ int fx_field_digest(fx_ctx* ctx, int field, uint32_t z_begin, uint32_t z_count, 
 	if (rc) return rc;
 	if (field > FX_FIELD_DIVERGENCE) return FX_E_INVALID;
 	const Geom& g = ctx->g;
+	if (!digest_range_ok(g, z_begin, z_count)) return FX_E_INVALID;
 	if (!z_count) { z_begin = (uint32_t)g.z0; z_count = (uint32_t)g.nz; }
-	if ((int)z_begin < g.z0 || z_begin + z_count > (uint32_t)(g.z0 + g.nz)) return FX_E_INVALID;
 	DeviceGuard dg(ctx->device);
 	FX_HIP(hipDeviceSynchronize());
 	if ((rc = halo_fault_status(ctx))) return rc;

@@ -83,6 +83,13 @@ struct EmitArgs { int n, x0, y0, z0, tiles_x, tiles_y, tiles_z; EmitBall e[FX_MA
 int emit_plan(const Geom& g, const fx_emitter* list, int count, EmitArgs* out);
 hipError_t launch_emit(const Geom& g, int half_store, void* vel, void* col, float* alpha, const fx_emitter* list, int count, float dt, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
+// ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
+// cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
+enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };
+enum SimRowKernel { ROW_SCALAR = 0, ROW_V4 = 4, ROW_VW2 = 2, ROW_VW3 = 3 };
+int sim_row_kernel(const Geom& g, int half_store, int stage, int is3d);       // is3d: SimParams::is3d (the projection's own 2-D / 3-D switch)
+// fx_field_digest's range rule: the planes [z_begin, z_begin + z_count) lie inside the owned planes (z_count = 0 stands for all of them)
+bool digest_range_ok(const Geom& g, uint32_t z_begin, uint32_t z_count);
 // one lock-step sweep p_in -> p_out on planes [z_begin, z_end); frozen may be null
 hipError_t launch_jacobi_sweep(const Geom& g, const float* p_in, const float* b, float* p_out, uint8_t* frozen,
 	int z_begin, int z_end, hipStream_t s);

@@ -762,13 +762,21 @@ __global__ __launch_bounds__(256) void k_project_vw(const Geom g, const typename
 	stwv<W, HALF>(vel_out, 2u * stride + off, oz);
 }
 
-// cells per thread of the vW kernels: 3 or 2 where that divides the row, 0 = none (the scalar kernels)
-static int vw_width(const Geom& g, int half_store)
+// Which kernel of the divergence / projection family serves a geometry (SimRowKernel): 16-byte vectors where rows and component planes keep
+// them aligned, else 3 or 2 cells per thread where that divides the row (binary16: pairs only -- 4-byte aligned in an even row), else
+// the scalar kernel.  The vector kernels are 3-D only; those with 32-bit offsets stop below 2^30 elements of velocity.
+int sim_row_kernel(const Geom& g, int half_store, int stage, int is3d)
 {
-	const int on = FX_KNOB_INT("ROW_VW", 1);
-	if (!on || g.Zg <= 1 || g.cells_local() * 3 >= ((size_t)1 << 30)) return 0;
-	if (half_store) return g.X % 2 == 0 ? 2 : 0;               // binary16: pairs (4-byte aligned in an even row)
-	return g.X % 3 == 0 ? 3 : (g.X % 2 == 0 ? 2 : 0);
+	const bool rows16 = (g.X & 3) == 0 && (g.cells_local() & 3) == 0, small = g.cells_local() * 3 < ((size_t)1 << 30);
+	if (stage == SIM_DIVERGENCE) {
+		if (g.Zg > 1 && rows16) return ROW_V4;
+	} else {
+		if (!is3d) return ROW_SCALAR;
+		if (FX_KNOB_INT("PROJECT_V4", 1) && rows16 && small) return ROW_V4;
+	}
+	if (!FX_KNOB_INT("ROW_VW", 1) || g.Zg <= 1 || !small) return ROW_SCALAR;
+	if (half_store) return g.X % 2 == 0 ? ROW_VW2 : ROW_SCALAR;
+	return g.X % 3 == 0 ? ROW_VW3 : (g.X % 2 == 0 ? ROW_VW2 : ROW_SCALAR);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -927,7 +935,8 @@ hipError_t launch_advect(const Geom& g, const SimParams& sp, int half_store, con
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s)
 {
 	if (z_end <= z_begin) return hipSuccess;
-	if (g.Zg > 1 && (g.X & 3) == 0 && (g.cells_local() & 3) == 0) {
+	const int w = sim_row_kernel(g, half_store, SIM_DIVERGENCE, g.Zg > 1);
+	if (w == ROW_V4) {
 		const int nzp = z_end - z_begin, X4 = g.X >> 2;
 		const int bx = X4 < 64 ? X4 : 64;
 		int by = 256 / bx; if (by > g.Y) by = g.Y;
@@ -936,7 +945,7 @@ hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, flo
 		else hipLaunchKernelGGL(k_divergence_v4<false>, grid, block, 0, s, g, (const float*)vel, b, z_begin, nzp, xcd_remap_for(REMAP_DIV, g), by);
 		return hipGetLastError();
 	}
-	if (const int w = vw_width(g, half_store)) {
+	if (w != ROW_SCALAR) {
 		const int nzp = z_end - z_begin, XW = g.X / w;
 		const int bx = XW < 64 ? XW : 64;
 		int by = 256 / bx; if (by > g.Y) by = g.Y;
@@ -1034,8 +1043,8 @@ hipError_t launch_project(const Geom& g, const SimParams& sp, int half_store, co
 {
 	if (rec_done) *rec_done = false;
 	if (z_end <= z_begin) return hipSuccess;
-	const int v4_on = FX_KNOB_INT("PROJECT_V4", 1);
-	if (v4_on && sp.is3d && (g.X & 3) == 0 && (g.cells_local() & 3) == 0 && g.cells_local() * 3 < ((size_t)1 << 30)) {
+	const int w = sim_row_kernel(g, half_store, SIM_PROJECT, sp.is3d);
+	if (w == ROW_V4) {
 		auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
 		const int nzp = z_end - z_begin, X4 = g.X >> 2;
 		const int bx = X4 < 64 ? X4 : 64;
@@ -1057,7 +1066,7 @@ hipError_t launch_project(const Geom& g, const SimParams& sp, int half_store, co
 #undef FX_PV4
 		return hipGetLastError();
 	}
-	if (const int w = sp.is3d ? vw_width(g, half_store) : 0) {
+	if (w != ROW_SCALAR) {
 		const int nzp = z_end - z_begin, XW = g.X / w;
 		const int bx = XW < 64 ? XW : 64;
 		int by = 256 / bx; if (by > g.Y) by = g.Y;

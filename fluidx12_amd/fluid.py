@@ -349,9 +349,12 @@ class Fluid:
     def digest(self, field, z_begin=0, z_count=0):
         """128-bit device-side digest (an int) of global planes [z_begin, z_begin + z_count) of a simulation field -- equal between a
         slab context and a single-domain context iff the planes agree bit for bit (fx_field_digest); z_count = 0: all owned planes"""
+        z_begin, z_count = int(z_begin), int(z_count)
+        if not (0 <= z_begin < 1 << 32 and 0 <= z_count < 1 << 32):     # ctypes would truncate to 32 bits without a word
+            raise ValueError("digest: z_begin and z_count must be in 0 .. 2^32 - 1, got %d, %d" % (z_begin, z_count))
         self._need()
         out = (C.c_uint64 * 2)()
-        capi.check(self._lib.fx_field_digest(self._ctx, field, int(z_begin), int(z_count), out), "digest")
+        capi.check(self._lib.fx_field_digest(self._ctx, field, z_begin, z_count, out), "digest")
         return (int(out[1]) << 64) | int(out[0])
 
     def upload(self, field, array):
