@@ -4,6 +4,7 @@
 //   hipcc -std=c++17 examples/fluidx_demo.cpp -o fluidx_demo -Lfluidx12_amd -lfluidx_hip -Wl,-rpath,$PWD/fluidx12_amd
 // Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
 //        [-emitter CX CY CZ R]... [-noimpulse]     (smoke sources, fx_set_emitters: texture space [0,1]^3, with the built-in's colour and lift; -noimpulse: without the reference's own source)
+//        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; the demo does not draw the ball itself)
 //        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
@@ -96,6 +97,8 @@ int main(int argc, char** argv)
 	float vorticity = 0.0f;                             // not in the reference: strength of the vorticity confinement, 0 = off
 	std::vector<fx_emitter> emitters;                   // not in the reference: its only source is the impulse inside its advection
 	bool noImpulse = false;
+	bool obstacleSet = false;                           // not in the reference: its only boundaries are the box's walls
+	float obstacle[4] = {};
 	bool lightSet = false, pointLight = false, colorSet = false, ambientSet = false;   // not in the reference: its light is three constants (Fluid.cpp:169-173)
 	float lightPos[3] = { 75.0f, 75.0f, -75.0f }, lightColor[4] = {}, ambient[4] = {};
 	for (int i = 1; i < argc; ++i) {
@@ -116,6 +119,7 @@ int main(int argc, char** argv)
 			emitters.push_back(e);
 		}
 		else if (!std::strcmp(argv[i], "-noimpulse")) noImpulse = true;
+		else if (!std::strcmp(argv[i], "-obstacle") && i + 4 < argc) { for (float& v : obstacle) v = (float)atof(argv[++i]); obstacleSet = true; }
 		else if (!std::strcmp(argv[i], "-light") && i + 3 < argc) { for (float& v : lightPos) v = (float)atof(argv[++i]); lightSet = true; }
 		else if (!std::strcmp(argv[i], "-pointLight")) { pointLight = true; lightSet = true; }
 		else if (!std::strcmp(argv[i], "-lightColor") && i + 4 < argc) { for (float& v : lightColor) v = (float)atof(argv[++i]); colorSet = lightSet = true; }
@@ -136,6 +140,17 @@ int main(int argc, char** argv)
 	}
 	if (!emitters.empty() && !fluid.SetEmitters(emitters)) { std::fprintf(stderr, "-emitter: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (noImpulse && !fluid.SetImpulse(false)) { std::fprintf(stderr, "-noimpulse: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	if (obstacleSet) {                                  // voxelise: the cells whose centre lies inside the ball
+		std::vector<uint8_t> solid((size_t)grid.x * grid.y * grid.z, 0);
+		for (uint32_t z = 0; z < grid.z; ++z)
+			for (uint32_t y = 0; y < grid.y; ++y)
+				for (uint32_t x = 0; x < grid.x; ++x) {
+					const float dx = (x + 0.5f) / grid.x - obstacle[0], dy = (y + 0.5f) / grid.y - obstacle[1];
+					const float dz = grid.z > 1 ? (z + 0.5f) / grid.z - obstacle[2] : 0.0f;
+					solid[((size_t)z * grid.y + y) * grid.x + x] = dx * dx + dy * dy + dz * dz <= obstacle[3] * obstacle[3] ? 1 : 0;
+				}
+		if (!fluid.SetObstacles(solid)) { std::fprintf(stderr, "-obstacle: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	}
 	if (lightSet && grid.z <= 1) std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: a 2-D grid has no light; ignored\n");
 	if (lightSet && grid.z > 1 && !fluid.SetLight(lightPos, pointLight, colorSet ? lightColor : nullptr, ambientSet ? ambient : nullptr)) {
 		std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: %s\n", fx_error_string(fluid.LastStatus()));

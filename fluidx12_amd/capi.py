@@ -24,6 +24,7 @@ ABI_VERSION = 7                      # FX_ABI_VERSION of include/fluidx_hip.h
 DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is device memory, read in place
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
+OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memory
 
 
 class Desc(C.Structure):
@@ -93,6 +94,9 @@ SYMBOLS = {
     "fx_get_emitters": (C.c_int, [_vp, C.POINTER(Emitter), C.c_uint32, C.POINTER(C.c_uint32)]),
     "fx_set_impulse": (C.c_int, [_vp, C.c_int]),
     "fx_emit": (C.c_int, [_vp, _vp]),
+    "fx_set_obstacles": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32]),
+    "fx_get_obstacles": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "fx_enforce_obstacles": (C.c_int, [_vp, _vp]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),
@@ -120,7 +124,7 @@ _lib = None
 # the launcher switches that exist in lab builds only (fx_knobs.cpp, -DFX_LAB)
 LAB_KNOBS = {"ADVECT_BLOCK", "ADVECT_FAST", "ADVECT_LDS_HALF", "ADVECT_TILE_ROWS", "ADVECT_ZCHUNK", "BLOCK_REMAP", "BLOCK_SHAPE", "DEBUG_NO_COPY",
              "FREEZE_DENSE_LEVELS", "FREEZE_DENSE_ONE", "FREEZE_FAST", "FREEZE_FUSE_DIV", "FREEZE_NT", "FREEZE_SHRINK", "FREEZE_T", "FREEZE_WGS",
-             "JACOBI2D_TILE", "JACOBI_BLOCK", "JACOBI_BLOCKG", "LIGHT_FILL_DIRTY", "LIGHT_RAY_NT", "LIGHT_RAY_WGS", "PROJECT_V4", "ROW_VW",
+             "JACOBI2D_TILE", "JACOBI_BLOCK", "JACOBI_BLOCKG", "LIGHT_FILL_DIRTY", "LIGHT_RAY_NT", "LIGHT_RAY_WGS", "OBSTACLE_V4", "PROJECT_V4", "ROW_VW",
              "STRIP3H_PAIRS", "STRIP3_COOP", "STRIP3_NO512", "STRIP3_OFF", "STRIP3_ZCHUNK", "STRIP4T", "STRIP4T_256", "STRIP4T_512", "STRIP4T_FROM", "STRIP4T_GRID", "STRIP4T_NARROW", "STRIP4T_NARROW_FROM", "STRIP4T_PIECES", "STRIP4X", "STRIP4X_MINP", "STRIP4X_NT", "STRIP4X_ORDER", "STRIP4X_WGS",
              "STRIP4_OCTET", "STRIP4_ZCHUNK", "STRIP4_ZFLOOR", "STRIP_GENERIC", "STRIP_R", "STRIP_REMAP", "STRIP_WGS", "STRIP_WIDE", "STRIP_ZCHUNK", "VIEW_ORDER", "VIEW_WGS", "VORT_ZCHUNK", "XCD_REMAP"}
 

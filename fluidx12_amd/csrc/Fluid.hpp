@@ -129,6 +129,23 @@ public:
 	// the emitter stage alone (fx_emit), beside the stage calls of the C interface
 	bool Emit(void* stream = nullptr) { m_status = fx_emit(m_ctx, stream); return m_status == FX_OK; }
 
+	// not in the reference (its only boundaries are the box's walls): voxelised solid obstacles the smoke flows around (fx_set_obstacles;
+	// mask uint8[Z][Y][X], non-zero = solid; nullptr detaches).  The caller draws the object itself and passes its depth with SetSceneDepth
+	bool SetObstacles(const uint8_t* solid, size_t bytes, void* stream = nullptr, bool deviceMemory = false)
+	{
+		m_status = fx_set_obstacles(m_ctx, stream, solid, bytes, deviceMemory ? FX_OBSTACLES_DEVICE : 0u);
+		return m_status == FX_OK;
+	}
+	bool SetObstacles(const std::vector<uint8_t>& solid) { return SetObstacles(solid.data(), solid.size()); }
+	bool GetObstacles(std::vector<uint8_t>& out, uint64_t* solidCells = nullptr)
+	{
+		out.assign(fx_field_bytes(m_ctx, FX_FIELD_PRESSURE) / sizeof(float), 0);        // one byte per cell
+		m_status = fx_get_obstacles(m_ctx, out.data(), out.size(), solidCells);
+		return m_status == FX_OK;
+	}
+	// the enforce stage alone (fx_enforce_obstacles), beside Emit
+	bool EnforceObstacles(void* stream = nullptr) { m_status = fx_enforce_obstacles(m_ctx, stream); return m_status == FX_OK; }
+
 	// not in the reference (its state dies with the window): whole-grid state files, see fx_checkpoint_save
 	bool SaveCheckpoint(const char* path) { m_status = fx_checkpoint_save(m_ctx, path); return m_status == FX_OK; }
 	bool LoadCheckpoint(const char* path) { m_status = fx_checkpoint_load(m_ctx, path); return m_status == FX_OK; }

@@ -459,6 +459,77 @@ int fx_emit(fx_ctx* ctx, void* stream)
 	return emit_phase(ctx, pick_stream(ctx, stream));
 }
 
+// ---- solid obstacles (fx_obstacle.hip) ------------------------------------------------------------------
+int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t bytes, uint32_t flags)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (flags & ~(uint32_t)FX_OBSTACLES_DEVICE) return FX_E_INVALID;
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the confinement's footing
+	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no obstacle-aware kernels
+	DeviceGuard dg(ctx->device);
+	if (!solid) {                                                           // detach: every launch is the plain one again
+		if (ctx->obst_code) {
+			if (ctx->obst_spare) FX_HIP(hipFree(ctx->obst_spare));          // (hipFree waits for the device: nothing reads the volume any more)
+			ctx->obst_spare = ctx->obst_code;
+			ctx->obst_code = nullptr;
+		}
+		ctx->obst_cells = 0;
+		return FX_OK;
+	}
+	const size_t n = ctx->g.plane() * (size_t)ctx->g.Zg;
+	if (bytes != n) return FX_E_INVALID;
+	hipStream_t s = pick_stream(ctx, stream);
+	// the new code volume is built beside the one in force, which stays in force if anything below fails
+	if (!ctx->obst_spare && hipMalloc((void**)&ctx->obst_spare, n) != hipSuccess) { (void)hipGetLastError(); ctx->obst_spare = nullptr; return FX_E_NOMEM; }
+	if (!ctx->obst_stats && hipMalloc((void**)&ctx->obst_stats, 8 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->obst_stats = nullptr; return FX_E_NOMEM; }
+	const uint8_t* src = solid;
+	if (!(flags & FX_OBSTACLES_DEVICE)) {
+		const int rc = ensure_stage(ctx, n);
+		if (rc) return rc;
+		FX_HIP(hipMemcpyAsync(ctx->stage, solid, n, hipMemcpyHostToDevice, s));
+		src = reinterpret_cast<const uint8_t*>(ctx->stage);
+	}
+	FX_HIP(launch_obstacle_codes(ctx->g, src, ctx->obst_spare, ctx->obst_stats, s));
+	unsigned st[8];
+	FX_HIP(hipMemcpyAsync(st, ctx->obst_stats, sizeof st, hipMemcpyDeviceToHost, s));
+	FX_HIP(hipStreamSynchronize(s));                                        // the count and the box size the enforce launch; `solid` is free again
+	std::swap(ctx->obst_code, ctx->obst_spare);
+	ctx->obst_cells = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
+	for (int a = 0; a < 3; ++a) {
+		ctx->obst_lo[a] = ctx->obst_cells ? (int)st[2 + a] : 0;
+		ctx->obst_hi[a] = ctx->obst_cells ? (int)st[5 + a] + 1 : 0;
+	}
+	return FX_OK;
+}
+
+int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	const size_t n = ctx->g.plane() * (size_t)ctx->g.Zg;
+	if (solid_out && bytes != n) return FX_E_INVALID;
+	if (solid_cells) *solid_cells = ctx->obst_code ? ctx->obst_cells : 0;
+	if (!solid_out) return FX_OK;
+	if (!ctx->obst_code) { std::memset(solid_out, 0, n); return FX_OK; }
+	DeviceGuard dg(ctx->device);
+	FX_HIP(hipDeviceSynchronize());
+	const int rc = ensure_stage(ctx, n);
+	if (rc) return rc;
+	FX_HIP(launch_obstacle_mask(ctx->obst_code, reinterpret_cast<uint8_t*>(ctx->stage), n, ctx->stream));
+	FX_HIP(hipMemcpyAsync(solid_out, ctx->stage, n, hipMemcpyDeviceToHost, ctx->stream));
+	FX_HIP(hipStreamSynchronize(ctx->stream));
+	return FX_OK;
+}
+
+int fx_enforce_obstacles(fx_ctx* ctx, void* stream)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	return enforce_phase(ctx, pick_stream(ctx, stream));
+}
+
 int fx_divergence(fx_ctx* ctx, void* stream)
 {
 	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;

@@ -63,6 +63,12 @@ struct fx_ctx {
 	// the smoke sources (fx_set_emitters / fx_set_impulse; configuration on the same terms)
 	std::vector<fx_emitter> emitters;   // applied by k_emit behind every advection, in this order; empty = none (default)
 	bool impulse_on = true;         // the reference's built-in impulse inside the advection kernels
+	// solid obstacles (fx_set_obstacles; configuration on the same terms): the code byte per cell the obstacle kernels read (fx_obstacle.hip)
+	uint8_t* obst_code = nullptr;   // device, X * Y * Z bytes; null = none: every launch is the plain one
+	uint8_t* obst_spare = nullptr;  // the previous code volume, kept for the next fx_set_obstacles (a moving obstacle allocates nothing)
+	unsigned* obst_stats = nullptr; // device, 8 words: what k_obstacle_codes counts
+	uint64_t obst_cells = 0;        // solid cells
+	int obst_lo[3] = { 0, 0, 0 }, obst_hi[3] = { 0, 0, 0 };   // their bounding box [lo, hi): what the enforce launch covers
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -83,6 +83,21 @@ struct EmitArgs { int n, x0, y0, z0, tiles_x, tiles_y, tiles_z; EmitBall e[FX_MA
 int emit_plan(const Geom& g, const fx_emitter* list, int count, EmitArgs* out);
 hipError_t launch_emit(const Geom& g, int half_store, void* vel, void* col, float* alpha, const fx_emitter* list, int count, float dt, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
+// ---- solid obstacles (fx_obstacle.hip), whole grids only (hipErrorNotSupported for a slab geometry).  code: one byte per cell, bits 0..5 = the
+// clamped neighbour at x-1, x+1, y-1, y+1, z-1, z+1 is solid (z bits 0 on 2-D grids), bit 6 = the cell is; the stencil launchers read it, never the mask
+// launch_obstacle_codes: solid_dev uint8[Z][Y][X] (device) -> code; stats_dev (8 device words) gets { solid cells (2 words, low first), min x, y, z, max x, y, z }
+hipError_t launch_obstacle_codes(const Geom& g, const uint8_t* solid_dev, uint8_t* code, unsigned* stats_dev, hipStream_t s);
+hipError_t launch_obstacle_mask(const uint8_t* code, uint8_t* solid_dev, size_t n, hipStream_t s);      // the 0 / 1 mask back out of the codes
+// the enforce launch's tiles: the solids' box [lo, hi) on the grid's 64 x 4 raster, first tile at (*x0, *y0, lo[2]) -> workgroups (host code)
+long long obstacle_enforce_tiles(const int lo[3], const int hi[3], int* x0, int* y0, int* tiles_x, int* tiles_y);
+// solid cells of vel (3 components) / col become +0, in place; alpha: the render's side volume when it holds this colour field's alpha, else null
+hipError_t launch_obstacle_enforce(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3], void* vel, void* col,
+	float* alpha, hipStream_t s);
+hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel, const uint8_t* code, float* b, int z_begin, int z_end, hipStream_t s);
+bool jacobi_obs_takes_v4(const Geom& g);     // 3-D, X % 4 == 0: four cells per thread; else the scalar kernel
+hipError_t launch_jacobi_obs(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, int z_begin, int z_end, hipStream_t s);   // one sweep
+hipError_t launch_project_obs(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	void* vel_out, int z_begin, int z_end, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

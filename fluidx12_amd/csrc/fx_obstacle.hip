@@ -1,0 +1,410 @@
+// fx_obstacle.hip -- voxelised solid obstacles inside the box (fx_set_obstacles), gfx950.  No reference counterpart: the reference's only
+// boundaries are the six walls (the clamped neighbour indices of its projection shaders); Harris / Crane et al. (GPU Gems 3, ch. 30) is the scheme.
+//
+//   k_obstacle_codes    mask uint8[Z][Y][X] -> one code byte per cell (+ the count of solid cells and their bounding box)
+//   k_obstacle_enforce  solid cells: VELOCITY1, COLOR (and the render's alpha side volume) become +0; over the solids' bounding box only
+//   k_divergence_obs    k_divergence with  v(n) -> S(n) ? 0 : v(n),  b = 0 in a solid cell
+//   k_jacobi_obs(_v4)   one lock-step sweep with  p(n) -> S(n) ? p(c) : p(n),  p_out = 0 in a solid cell
+//   k_project_obs       k_project with the same pressure substitution, u[a] = 0 beside a solid along a (free slip), 0 in a solid cell
+//
+// The wall rule of the plain kernels is "a neighbour that is not there reads as the cell itself" (clamped indices); a solid extends it to
+// neighbours inside an obstacle.  The stencil kernels never read the mask: the code byte of a cell holds S of its six CLAMPED neighbours
+// (bit 0..5: x-1, x+1, y-1, y+1, z-1, z+1; the z bits are 0 on 2-D grids) and of the cell itself (bit 6), built once per fx_set_obstacles.
+// Every substitution is a select on a loaded value -- no branch, no divergence -- and with an all-zero mask each kernel is, operation for
+// operation, its plain counterpart of fx_sim.hip (tests/test_gpu_obstacles.py holds them bit for bit against each other and against
+// tests/obstacle_ref/).  fp32 arithmetic in the plain kernels' association order; fp16 storage widens on load and rounds once (RNE) on store.
+// Whole grids only (fx_set_obstacles refuses slab ranks): local plane = global plane.
+#include "fx_internal.h"
+
+namespace fx {
+
+namespace {
+
+typedef _Float16 h16;
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+
+enum { OB_XM = 1, OB_XP = 2, OB_YM = 4, OB_YP = 8, OB_ZM = 16, OB_ZP = 32, OB_SELF = 64 };
+
+// velocity / colour storage: fp32, or binary16 rounded from the fp32 result in a step of its own (the empty asm keeps the producing
+// multiply and the conversion apart -- the same device as Store<true> of fx_sim.hip)
+template <bool HALF> struct Sto;
+template <> struct Sto<false> {
+	typedef float S;
+	typedef float4 S4;
+	static __device__ __forceinline__ float ld(const S* p, size_t i) { return p[i]; }
+	static __device__ __forceinline__ void st(S* p, size_t i, float v) { p[i] = v; }
+	static __device__ __forceinline__ void zero4(S4* p, size_t i) { p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+};
+template <> struct Sto<true> {
+	typedef h16 S;
+	typedef h16x4 S4;
+	static __device__ __forceinline__ float ld(const S* p, size_t i) { return (float)p[i]; }
+	static __device__ __forceinline__ void st(S* p, size_t i, float v) { asm("" : "+v"(v)); p[i] = (h16)v; }
+	static __device__ __forceinline__ void zero4(S4* p, size_t i) { h16x4 h; h.x = h.y = h.z = h.w = (h16)0.0f; p[i] = h; }
+};
+
+// workgroup -> tile, the mapping of the plain kernels (fx_sim.hip xcd_tile): remap 1 = XCD k walks the k-th contiguous eighth of the
+// (x, y, z)-ordered tile sequence, 0 = natural order.  Speed only.
+struct Tile3 { int x, y, z; };
+__device__ __forceinline__ Tile3 tile_of(int gx, int gy, int gz, int remap)
+{
+	int t = (int)blockIdx.x;
+	if (remap == 1) {
+		const int n = gx * gy * gz, q = n >> 3, r = n & 7;
+		const int xcd = t & 7, j = t >> 3;
+		t = xcd * q + min(xcd, r) + j;
+	}
+	Tile3 o;
+	o.x = t % gx;
+	const int u = t / gx;
+	o.y = u % gy;
+	o.z = u / gy;
+	return o;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// code bytes.  stats: { solid cells (two words, low first), min x, y, z, max x, y, z } -- zeroed / set to (INT_MAX, 0) by the launcher
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_obstacle_codes(const Geom g, const uint8_t* __restrict__ solid, uint8_t* __restrict__ code,
+	unsigned* __restrict__ stats)
+{
+	const int gx = (g.X + 63) >> 6, gy = (g.Y + 3) >> 2;
+	int t = (int)blockIdx.x;
+	const int tx = t % gx; t /= gx;
+	const int x = tx * 64 + (int)threadIdx.x, y = (t % gy) * 4 + (int)threadIdx.y, z = t / gy;
+	const bool in = x < g.X && y < g.Y;
+	unsigned self = 0;
+	if (in) {
+		const size_t plane = g.plane();
+		const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
+		const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
+		const size_t zrow = (size_t)z * plane, row = zrow + (size_t)y * g.X;
+		unsigned k = 0;
+		self = solid[row + x] ? 1u : 0u;
+		k |= solid[row + xl] ? OB_XM : 0;
+		k |= solid[row + xr] ? OB_XP : 0;
+		k |= solid[zrow + (size_t)yu * g.X + x] ? OB_YM : 0;
+		k |= solid[zrow + (size_t)yd * g.X + x] ? OB_YP : 0;
+		if (g.Zg > 1) {
+			const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
+			k |= solid[(size_t)zf * plane + (size_t)y * g.X + x] ? OB_ZM : 0;
+			k |= solid[(size_t)zb * plane + (size_t)y * g.X + x] ? OB_ZP : 0;
+		}
+		k |= self ? OB_SELF : 0;
+		code[row + x] = (uint8_t)k;
+	}
+	// one wave = one row of the tile: its solid cells share y and z
+	const unsigned long long m = __builtin_amdgcn_ballot_w64(self != 0);
+	if (m == 0 || (threadIdx.x & 63) != 0) return;
+	const int x0 = tx * 64;
+	const unsigned n = (unsigned)__builtin_popcountll(m);
+	if (atomicAdd(stats, n) + n < n) atomicAdd(stats + 1, 1u);              // carry into the high word
+	atomicMin(reinterpret_cast<int*>(stats) + 2, x0 + (int)__builtin_ctzll(m));
+	atomicMax(reinterpret_cast<int*>(stats) + 5, x0 + 63 - (int)__builtin_clzll(m));
+	atomicMin(reinterpret_cast<int*>(stats) + 3, y); atomicMax(reinterpret_cast<int*>(stats) + 6, y);
+	atomicMin(reinterpret_cast<int*>(stats) + 4, z); atomicMax(reinterpret_cast<int*>(stats) + 7, z);
+}
+
+// the mask back out of the code bytes (fx_get_obstacles): 0 / 1 per cell
+__global__ __launch_bounds__(256) void k_obstacle_mask(const uint8_t* __restrict__ code, uint8_t* __restrict__ solid, size_t n)
+{
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) solid[i] = (code[i] >> 6) & 1u;
+}
+
+// ---------------------------------------------------------------------------------------------
+// enforce: 64 x 4 x 1 tiles on the grid's own raster over the solids' bounding box, first tile at (x0, y0, z0)
+// ---------------------------------------------------------------------------------------------
+template <bool HALF>
+__global__ __launch_bounds__(256) void k_obstacle_enforce(const Geom g, const uint8_t* __restrict__ code, typename Sto<HALF>::S* __restrict__ vel,
+	typename Sto<HALF>::S4* __restrict__ col, float* __restrict__ alpha, int x0, int y0, int z0, int tiles_x, int tiles_y)
+{
+	typedef Sto<HALF> St;
+	int t = (int)blockIdx.x;
+	const int x = x0 + (t % tiles_x) * 64 + (int)threadIdx.x; t /= tiles_x;
+	const int y = y0 + (t % tiles_y) * 4 + (int)threadIdx.y, z = z0 + t / tiles_y;
+	if (x >= g.X || y >= g.Y) return;
+	const size_t stride = g.cells_local();
+	const size_t id = (size_t)g.lz(z) * g.plane() + (size_t)y * g.X + x;
+	if (!(code[id] & OB_SELF)) return;                       // fluid cells keep their bits
+	St::st(vel, id, 0.0f);
+	St::st(vel, stride + id, 0.0f);
+	St::st(vel, 2 * stride + id, 0.0f);
+	St::zero4(col, id);
+	if (alpha) alpha[id] = 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------
+// divergence  b = 0.5 * (ddz + (ddy + ddx)), dd = -v(n-) + v(n+), a neighbour inside a solid reads as 0 (the solids are at rest)
+// ---------------------------------------------------------------------------------------------
+template <bool HALF>
+__global__ __launch_bounds__(256) void k_divergence_obs(const Geom g, const typename Sto<HALF>::S* __restrict__ vel, const uint8_t* __restrict__ code,
+	float* __restrict__ b, int z_begin, int nzp, int remap)
+{
+	typedef Sto<HALF> St;
+	const Tile3 tile = tile_of((g.X + 63) >> 6, (g.Y + 3) >> 2, nzp, remap);
+	const int x = tile.x * 64 + threadIdx.x;
+	const int y = tile.y * 4 + threadIdx.y;
+	const int z = z_begin + tile.z;
+	if (x >= g.X || y >= g.Y) return;
+	const size_t plane = g.plane(), stride = g.cells_local();
+	const size_t zrow = (size_t)g.lz(z) * plane, row = zrow + (size_t)y * g.X;
+	const unsigned k = code[row + x];
+	const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
+	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
+	const float vl = St::ld(vel, row + xl), vr = St::ld(vel, row + xr);
+	const float vu = St::ld(vel, stride + zrow + (size_t)yu * g.X + x), vd = St::ld(vel, stride + zrow + (size_t)yd * g.X + x);
+	const float ddx = -((k & OB_XM) ? 0.0f : vl) + ((k & OB_XP) ? 0.0f : vr);
+	const float ddy = -((k & OB_YM) ? 0.0f : vu) + ((k & OB_YP) ? 0.0f : vd);
+	float S;
+	if (g.Zg > 1) {
+		const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
+		const float vf = St::ld(vel, 2 * stride + (size_t)g.lz(zf) * plane + (size_t)y * g.X + x);
+		const float vb = St::ld(vel, 2 * stride + (size_t)g.lz(zb) * plane + (size_t)y * g.X + x);
+		const float ddz = -((k & OB_ZM) ? 0.0f : vf) + ((k & OB_ZP) ? 0.0f : vb);
+		S = ddz + (ddy + ddx);
+	} else {
+		S = ddx + ddy;
+	}
+	b[row + x] = (k & OB_SELF) ? 0.0f : 0.5f * S;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Jacobi sweep, scalar: any extent, 2-D / 3-D
+//   x = ((((((qL - b) + qR) + qU) + qD) + qF) + qB) * (1/6)     2-D: ((((qL - b) + qR) + qU) + qD) * 1/4,   q(n) = S(n) ? p(c) : p(n)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_jacobi_obs(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
+	const uint8_t* __restrict__ code, float* __restrict__ p_out, int z_begin, int nzp, int remap)
+{
+	const Tile3 tile = tile_of((g.X + 63) >> 6, (g.Y + 3) >> 2, nzp, remap);
+	const int x = tile.x * 64 + threadIdx.x;
+	const int y = tile.y * 4 + threadIdx.y;
+	const int z = z_begin + tile.z;
+	if (x >= g.X || y >= g.Y) return;
+	const size_t plane = g.plane();
+	const size_t zrow = (size_t)g.lz(z) * plane;
+	const size_t id = zrow + (size_t)y * g.X + x;
+	const unsigned k = code[id];
+	const float c = p_in[id];
+	const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
+	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
+	const float L = p_in[zrow + (size_t)y * g.X + xl], R = p_in[zrow + (size_t)y * g.X + xr];
+	const float U = p_in[zrow + (size_t)yu * g.X + x], D = p_in[zrow + (size_t)yd * g.X + x];
+	float s = ((k & OB_XM) ? c : L) - b[id];
+	s = ((k & OB_XP) ? c : R) + s;
+	s = ((k & OB_YM) ? c : U) + s;
+	s = ((k & OB_YP) ? c : D) + s;
+	float inv = 0.25f;
+	if (g.Zg > 1) {
+		const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
+		const float F = p_in[(size_t)g.lz(zf) * plane + (size_t)y * g.X + x], B = p_in[(size_t)g.lz(zb) * plane + (size_t)y * g.X + x];
+		s = ((k & OB_ZM) ? c : F) + s;
+		s = ((k & OB_ZP) ? c : B) + s;
+		inv = __uint_as_float(0x3e2aaaabu);
+	}
+	p_out[id] = (k & OB_SELF) ? 0.0f : s * inv;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Jacobi sweep, 3-D, X % 4 == 0: k_jacobi_v4's scheme (one thread = 4 consecutive x: 16-byte loads of the five p rows and of b, a 16-byte
+// store, the x neighbours of the row's ends through DPP lane shifts) + ONE 4-byte load for the four cells' codes: 13 bytes per cell and
+// sweep against 12.  Twenty-four selects and four for the solid cells themselves; bit-identical to k_jacobi_obs.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_jacobi_obs_v4(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
+	const uint8_t* __restrict__ code, float* __restrict__ p_out, int z_begin, int nzp, int remap, int rows_per_block)
+{
+	const int X4 = g.X >> 2;
+	const int lane = threadIdx.x;                       // float4 column
+	const Tile3 tile = tile_of((X4 + (int)blockDim.x - 1) / (int)blockDim.x, (g.Y + rows_per_block - 1) / rows_per_block, nzp, remap);
+	const int x4 = tile.x * blockDim.x + lane;
+	const int y = tile.y * rows_per_block + threadIdx.y;
+	const int z = z_begin + tile.z;
+	if (x4 >= X4 || y >= g.Y) return;
+	const size_t plane = g.plane();
+	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
+	const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
+	const size_t zrow = (size_t)g.lz(z) * plane;
+	const size_t c_off = zrow + (size_t)y * g.X + 4 * x4;
+	const float4 c = *reinterpret_cast<const float4*>(p_in + c_off);
+	const float4 U = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yu * g.X + 4 * x4);
+	const float4 D = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yd * g.X + 4 * x4);
+	const float4 F = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zf) * plane + (size_t)y * g.X + 4 * x4);
+	const float4 B = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zb) * plane + (size_t)y * g.X + 4 * x4);
+	const float4 bb = *reinterpret_cast<const float4*>(b + c_off);
+	const uint32_t kk = *reinterpret_cast<const uint32_t*>(code + c_off);      // (X % 4 == 0: every group of four cells is 4-byte aligned)
+	// x neighbours: the adjacent float4 column sits in the adjacent lane (DPP wave_shr:1 / wave_shl:1, as k_jacobi_v4); only a wave's
+	// first / last lane inside a row still loads them
+	const int wl = (int)((threadIdx.y * blockDim.x + threadIdx.x) & 63);
+	float L = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, c.w), 0x138, 0xf, 0xf, false));
+	float R = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, c.x), 0x130, 0xf, 0xf, false));
+	if (x4 == 0) L = c.x; else if (wl == 0 || lane == 0) L = p_in[c_off - 1];
+	if (x4 == X4 - 1) R = c.w; else if (wl == 63 || lane == (int)blockDim.x - 1) R = p_in[c_off + 4];
+	const float inv = __uint_as_float(0x3e2aaaabu);
+	const float pc[4] = { c.x, c.y, c.z, c.w };
+	const float pl[4] = { L, c.x, c.y, c.z }, pr[4] = { c.y, c.z, c.w, R };
+	const float pu[4] = { U.x, U.y, U.z, U.w }, pd[4] = { D.x, D.y, D.z, D.w };
+	const float pf[4] = { F.x, F.y, F.z, F.w }, pb[4] = { B.x, B.y, B.z, B.w };
+	const float bv[4] = { bb.x, bb.y, bb.z, bb.w };
+	float o[4];
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		const unsigned k = kk >> (8 * i);
+		float s = ((k & OB_XM) ? pc[i] : pl[i]) - bv[i];
+		s = ((k & OB_XP) ? pc[i] : pr[i]) + s;
+		s = ((k & OB_YM) ? pc[i] : pu[i]) + s;
+		s = ((k & OB_YP) ? pc[i] : pd[i]) + s;
+		s = ((k & OB_ZM) ? pc[i] : pf[i]) + s;
+		s = ((k & OB_ZP) ? pc[i] : pb[i]) + s;
+		o[i] = (k & OB_SELF) ? 0.0f : s * inv;
+	}
+	*reinterpret_cast<float4*>(p_out + c_off) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// projection + free slip against the solids + wall damping
+// ---------------------------------------------------------------------------------------------
+template <bool HALF>
+__global__ __launch_bounds__(256) void k_project_obs(const Geom g, const SimParams sp,
+	const typename Sto<HALF>::S* __restrict__ vel_in, const float* __restrict__ p, const uint8_t* __restrict__ code,
+	typename Sto<HALF>::S* __restrict__ vel_out, int z_begin, int nzp, int remap)
+{
+	typedef Sto<HALF> St;
+	const Tile3 tile = tile_of((g.X + 63) >> 6, (g.Y + 3) >> 2, nzp, remap);
+	const int x = tile.x * 64 + threadIdx.x;
+	const int y = tile.y * 4 + threadIdx.y;
+	const int z = z_begin + tile.z;
+	if (x >= g.X || y >= g.Y) return;
+	const size_t plane = g.plane(), stride = g.cells_local();
+	const size_t zrow = (size_t)g.lz(z) * plane;
+	const size_t id = zrow + (size_t)y * g.X + x;
+	const unsigned k = code[id];
+	const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
+	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
+	float u[3] = { St::ld(vel_in, id), St::ld(vel_in, stride + id), St::ld(vel_in, 2 * stride + id) };
+	const float c = p[id];
+	const float L = p[zrow + (size_t)y * g.X + xl], R = p[zrow + (size_t)y * g.X + xr];
+	const float U = p[zrow + (size_t)yu * g.X + x], D = p[zrow + (size_t)yd * g.X + x];
+	float grad[3];
+	grad[0] = -((k & OB_XM) ? c : L) + ((k & OB_XP) ? c : R);
+	grad[1] = -((k & OB_YM) ? c : U) + ((k & OB_YP) ? c : D);
+	grad[2] = 0.0f;
+	float kd = 0.5f;
+	if (sp.is3d) {
+		const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
+		const float F = p[(size_t)g.lz(zf) * plane + (size_t)y * g.X + x], B = p[(size_t)g.lz(zb) * plane + (size_t)y * g.X + x];
+		grad[2] = -((k & OB_ZM) ? c : F) + ((k & OB_ZP) ? c : B);
+		kd = __uint_as_float(0x3f855556u);                                 // 0.5f / 0.48f, as k_project
+		u[2] = fmaf(-grad[2], kd, u[2]);
+	}
+	u[0] = fmaf(-grad[0], kd, u[0]);
+	u[1] = fmaf(-grad[1], kd, u[1]);
+	// free slip against a resting solid: no flow along an axis on which a neighbour is solid (the z bits are 0 on 2-D grids)
+	if (k & (OB_XM | OB_XP)) u[0] = 0.0f;
+	if (k & (OB_YM | OB_YP)) u[1] = 0.0f;
+	if (k & (OB_ZM | OB_ZP)) u[2] = 0.0f;
+	const int cell[3] = { x, y, z };
+	const float dims[3] = { (float)g.X, (float)g.Y, (float)g.Zg };
+#pragma unroll
+	for (int a = 0; a < 3; ++a) {                                          // the wall damping of k_project
+		float pos = ((float)cell[a] + 0.5f) / dims[a];
+		if (sp.is3d || a < 2) pos = fmaf(pos, 2.0f, -1.0f);
+		float f = (-fabsf(pos) + 0.970000029f) * 33.3333359f;
+		f = fminf(fmaxf(f, -1.0f), 1.0f);
+		const float w = (0.0f < u[a] * pos) ? f : 1.0f;
+		St::st(vel_out, a * stride + id, (k & OB_SELF) ? 0.0f : u[a] * w);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------
+static inline bool whole_grid(const Geom& g) { return g.nz == g.Zg && g.H == 0; }
+static inline dim3 grid_cells(const Geom& g, int nzp) { return dim3(((g.X + 63) / 64) * ((g.Y + 3) / 4) * nzp, 1, 1); }
+// the plain kernels' defaults (fx_sim.hip xcd_remap_for): the sweeps always take the contiguous-eighth order, divergence and projection on
+// the small 3-D grids that live in L2
+static inline int remap_small(const Geom& g) { return g.Zg > 1 && g.plane() <= 32768 && g.cells_local() < (size_t)6 << 20 ? 1 : 0; }
+
+hipError_t launch_obstacle_codes(const Geom& g, const uint8_t* solid_dev, uint8_t* code, unsigned* stats_dev, hipStream_t s)
+{
+	if (!whole_grid(g)) return hipErrorNotSupported;
+	const unsigned init[8] = { 0u, 0u, 0x7fffffffu, 0x7fffffffu, 0x7fffffffu, 0u, 0u, 0u };
+	hipError_t e = hipMemcpyAsync(stats_dev, init, sizeof init, hipMemcpyHostToDevice, s);     // (pageable source: copied out before the call returns)
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_obstacle_codes, grid_cells(g, g.Zg), dim3(64, 4, 1), 0, s, g, solid_dev, code, stats_dev);
+	return hipGetLastError();
+}
+
+hipError_t launch_obstacle_mask(const uint8_t* code, uint8_t* solid_dev, size_t n, hipStream_t s)
+{
+	if (!n) return hipSuccess;
+	const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+	hipLaunchKernelGGL(k_obstacle_mask, dim3(grid), dim3(256), 0, s, code, solid_dev, n);
+	return hipGetLastError();
+}
+
+// the tiles of the enforce launch: the box [lo, hi) on the grid's 64 x 4 raster -> workgroups (host code, no device needed)
+long long obstacle_enforce_tiles(const int lo[3], const int hi[3], int* x0, int* y0, int* tiles_x, int* tiles_y)
+{
+	if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return 0;
+	*x0 = lo[0] & ~63; *y0 = lo[1] & ~3;
+	*tiles_x = (hi[0] - *x0 + 63) / 64; *tiles_y = (hi[1] - *y0 + 3) / 4;
+	return (long long)*tiles_x * *tiles_y * (hi[2] - lo[2]);
+}
+
+hipError_t launch_obstacle_enforce(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3], void* vel, void* col,
+	float* alpha, hipStream_t s)
+{
+	if (!whole_grid(g)) return hipErrorNotSupported;
+	int x0, y0, tx, ty;
+	const long long wgs = obstacle_enforce_tiles(lo, hi, &x0, &y0, &tx, &ty);
+	if (wgs <= 0) return hipSuccess;                                          // no solid cell: nothing to launch
+	if (wgs > 0x7fffffffLL || hi[0] > g.X || hi[1] > g.Y || hi[2] > g.Zg || lo[0] < 0 || lo[1] < 0 || lo[2] < 0) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)wgs, 1, 1), block(64, 4, 1);
+	if (half_store) hipLaunchKernelGGL(k_obstacle_enforce<true>, grid, block, 0, s, g, code, (h16*)vel, (h16x4*)col, alpha, x0, y0, lo[2], tx, ty);
+	else hipLaunchKernelGGL(k_obstacle_enforce<false>, grid, block, 0, s, g, code, (float*)vel, (float4*)col, alpha, x0, y0, lo[2], tx, ty);
+	return hipGetLastError();
+}
+
+hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel, const uint8_t* code, float* b, int z_begin, int z_end, hipStream_t s)
+{
+	if (!whole_grid(g)) return hipErrorNotSupported;
+	if (z_end <= z_begin) return hipSuccess;
+	const dim3 grid = grid_cells(g, z_end - z_begin), block(64, 4, 1);
+	if (half_store) hipLaunchKernelGGL(k_divergence_obs<true>, grid, block, 0, s, g, (const h16*)vel, code, b, z_begin, z_end - z_begin, remap_small(g));
+	else hipLaunchKernelGGL(k_divergence_obs<false>, grid, block, 0, s, g, (const float*)vel, code, b, z_begin, z_end - z_begin, remap_small(g));
+	return hipGetLastError();
+}
+
+// OBSTACLE_V4 = 0 (lab builds): the scalar kernel on every geometry -- what tests/test_gpu_obstacles.py holds the wide one against
+bool jacobi_obs_takes_v4(const Geom& g) { return g.Zg > 1 && (g.X & 3) == 0 && FX_KNOB_INT("OBSTACLE_V4", 1) != 0; }
+
+hipError_t launch_jacobi_obs(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, int z_begin, int z_end, hipStream_t s)
+{
+	if (!whole_grid(g)) return hipErrorNotSupported;
+	const int nzp = z_end - z_begin;
+	if (nzp <= 0) return hipSuccess;
+	if (jacobi_obs_takes_v4(g)) {
+		const int X4 = g.X >> 2;                         // the block shape of k_jacobi_v4's launch
+		const int bx = X4 < 64 ? X4 : 64;
+		int by = 256 / bx; if (by < 1) by = 1; if (by > g.Y) by = g.Y;
+		const dim3 block(bx, by, 1), grid(((X4 + bx - 1) / bx) * ((g.Y + by - 1) / by) * nzp, 1, 1);
+		hipLaunchKernelGGL(k_jacobi_obs_v4, grid, block, 0, s, g, p_in, b, code, p_out, z_begin, nzp, 1, by);
+	} else {
+		hipLaunchKernelGGL(k_jacobi_obs, grid_cells(g, nzp), dim3(64, 4, 1), 0, s, g, p_in, b, code, p_out, z_begin, nzp, 1);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_project_obs(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	void* vel_out, int z_begin, int z_end, hipStream_t s)
+{
+	if (!whole_grid(g)) return hipErrorNotSupported;
+	if (z_end <= z_begin) return hipSuccess;
+	const dim3 grid = grid_cells(g, z_end - z_begin), block(64, 4, 1);
+	if (half_store) hipLaunchKernelGGL(k_project_obs<true>, grid, block, 0, s, g, sp, (const h16*)vel_in, p, code, (h16*)vel_out, z_begin, z_end - z_begin, remap_small(g));
+	else hipLaunchKernelGGL(k_project_obs<false>, grid, block, 0, s, g, sp, (const float*)vel_in, p, code, (float*)vel_out, z_begin, z_end - z_begin, remap_small(g));
+	return hipGetLastError();
+}
+
+}  // namespace fx

@@ -311,11 +311,29 @@ int emit_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// Solid obstacles (fx_obstacle.hip): behind the advection and the emitters, in front of the confinement, the solid cells of the advected velocity
+// and colour become +0, in place -- one launch over the solids' bounding box, booked with the advection like the two passes around it.  When this
+// step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well (the emitters' condition).
+int enforce_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->obst_code || !ctx->obst_cells || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	const int par = ctx->frame_parity;
+	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
+	FX_HIP(launch_obstacle_enforce(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->vel[1], ctx->col[par], alpha, s));
+	return FX_OK;
+}
+
 int divergence_phase(fx_ctx* ctx, hipStream_t s)
 {
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_DIV);
 	const Range r = owned(ctx);
+	if (ctx->obst_code) {
+		FX_HIP(launch_divergence_obs(ctx->g, ctx->half, ctx->vel[1], ctx->obst_code, ctx->b, r.lo, r.hi, s));
+		return FX_OK;
+	}
 	FX_HIP(launch_divergence(ctx->g, ctx->half, ctx->vel[1], ctx->b, r.lo, r.hi, s));
 	return FX_OK;
 }
@@ -614,8 +632,26 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 #undef FX_FIN
 }
 
+// With obstacles set (a whole-grid context in fixed mode: fx_set_obstacles refuses the others) the solve is `iters` single-sweep launches of the
+// obstacle-aware kernel, the wide one where it applies; FX_FLAG_JACOBI_FUSE_MASK is ignored and the planner is not asked.  (Several
+// obstacle-aware sweeps per launch, in the manner of the strip and block families, do not exist yet.)
+static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
+{
+	fx_ctx* ctx = lead;                                                 // FX_HIP reports through `ctx`
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_JACOBI);
+	const Range r = owned(ctx);
+	for (uint32_t i = 0; i < iters; ++i) {
+		FX_HIP(launch_jacobi_obs(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], r.lo, r.hi, s));
+		ctx->p_cur ^= 1;
+		mk.launches += 1; mk.sweeps += 1;
+	}
+	return FX_OK;
+}
+
 int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters)
 {
+	if (lead->obst_code) return jacobi_obstacle(lead, s, iters);
 	if (overlap_level(lead) >= 2) {
 		std::vector<JacobiPolicy> pol{ policy_of(lead) };
 		for (fx_ctx* m : M) pol.push_back(policy_of(m));
@@ -637,6 +673,10 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	const Range r = owned(ctx);
 	int* rec = multi_rank(ctx) ? ctx->step_rec : nullptr;           // slab ranks: the projection also measures the next advection's need
 	ctx->rec_in_project = false;
+	if (ctx->obst_code) {
+		FX_HIP(launch_project_obs(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], r.lo, r.hi, s));
+		return FX_OK;
+	}
 	FX_HIP(launch_project(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->vel[0], r.lo, r.hi, s,
 		rec, rec ? options_digest(ctx) : 0, ctx->halo_overflow, &ctx->rec_in_project));
 	return FX_OK;
@@ -659,6 +699,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
 		for (fx_ctx* m : M) if ((rc = emit_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with emitters set only)
+		for (fx_ctx* m : M) if ((rc = enforce_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with obstacles set only)
 		for (fx_ctx* m : M) if ((rc = confine_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with epsilon > 0 only)
 		const ExchSpec uz{ EX_UZ1, 1, 0 };
 		if ((rc = do_exchange(ctx, M, &uz, 1, ON_COMPUTE, s))) return rc;

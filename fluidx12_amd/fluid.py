@@ -304,6 +304,37 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_emit(self._ctx, stream), "Emit")
 
+    def SetObstacles(self, mask, stream=None):
+        """voxelised solid obstacles the smoke flows around (fx_set_obstacles): `mask` is anything numpy takes as an array of grid shape
+        (Z, Y, X) -- or X * Y * Z values in that order --, non-zero = solid; a torch tensor on the context's device is read in place; None
+        detaches.  Replaces the previous mask.  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid, fixed-mode contexts only."""
+        self._need()
+        if mask is None:
+            capi.check(self._lib.fx_set_obstacles(self._ctx, stream, None, 0, 0), "SetObstacles")
+            return
+        if hasattr(mask, "data_ptr") and getattr(mask, "is_cuda", False):
+            import torch
+            t = (mask != 0).to(dtype=torch.uint8).contiguous()
+            torch.cuda.current_stream(t.device).synchronize()      # the tensor was made on torch's stream, the library reads it on its own
+            capi.check(self._lib.fx_set_obstacles(self._ctx, stream, t.data_ptr(), t.numel(), capi.OBSTACLES_DEVICE), "SetObstacles")
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        capi.check(self._lib.fx_set_obstacles(self._ctx, stream, m.ctypes.data, m.size, 0), "SetObstacles")
+
+    def GetObstacles(self):
+        """(mask uint8 (Z, Y, X) of 0 / 1, solid cells) in force (fx_get_obstacles); all 0 when none"""
+        self._need()
+        X, Y, Z = self.grid
+        m = np.empty((Z, Y, X), np.uint8)
+        n = C.c_uint64(0)
+        capi.check(self._lib.fx_get_obstacles(self._ctx, m.ctypes.data, m.size, C.byref(n)), "GetObstacles")
+        return m, int(n.value)
+
+    def EnforceObstacles(self, stream=None):
+        """the enforce stage alone, in place on VELOCITY1 and COLOR (fx_enforce_obstacles); Advect does not include it"""
+        self._need()
+        capi.check(self._lib.fx_enforce_obstacles(self._ctx, stream), "EnforceObstacles")
+
     def Divergence(self, stream=None):
         capi.check(self._lib.fx_divergence(self._ctx, stream), "Divergence")
 

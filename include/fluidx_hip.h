@@ -332,6 +332,40 @@ int fx_get_emitters(fx_ctx* ctx, fx_emitter* out, uint32_t capacity, uint32_t* c
 int fx_set_impulse(fx_ctx* ctx, int enabled);
 int fx_emit(fx_ctx* ctx, void* stream);
 
+/* Solid obstacles inside the box (no reference counterpart: the reference's only boundaries are the six walls -- the clamped neighbour indices
+ * of its divergence, relaxation and projection; voxelised solids after Harris / Crane et al., GPU Gems 3 ch. 30).  fx_set_obstacles gives the
+ * context a mask S = uint8[Z][Y][X], non-zero = solid, resting (velocity 0).  The wall rule is "a neighbour that is not there reads as the cell
+ * itself"; a solid extends it to neighbours inside an obstacle.  In index space, n-a / n+a = the neighbours of cell c along axis a with the
+ * index clamped to the grid exactly as without obstacles, every operation rounded as in the plain stages:
+ *   enforce     (a pass of its own behind the advection and the emitters, in front of the confinement; dt > 0 only) a solid cell's VELOCITY1 and
+ *               COLOR components become +0; fluid cells keep their bits
+ *   divergence  b = 0.5 * (ddz + (ddy + ddx)) (2-D: ddx + ddy), dd = -v(n-) + v(n+) with v(n) read as S(n) ? 0 : v(n); b = 0 in a solid cell
+ *   relaxation  ((((((L - b) + R) + U) + D) + F) + B) * (1/6) (2-D: four terms, * 0.25), each neighbour S(n) ? p(c) : p(n); 0 in a solid cell
+ *   projection  grad_a = -(S(n-) ? p(c) : p(n-)) + (S(n+) ? p(c) : p(n+)), u[a] = fma(-grad_a, k, u[a]); then u[a] = 0 where S(n-a) | S(n+a)
+ *               (free slip against a resting solid); then the wall damping; 0 in all three components of a solid cell
+ * With an all-zero mask the three stages are, operation for operation, the plain ones (tests/obstacle_ref/ restates all four in C++).
+ * The stages read one code byte per cell, built on the device once per call (one upload + one launch: a moving obstacle is a new call per
+ * frame); the pressure solve then runs one obstacle-aware sweep per launch and ignores FX_FLAG_JACOBI_FUSE_MASK.
+ * Rendering is unchanged: a solid cell holds no smoke; the caller draws the object and passes its depth with fx_set_scene_depth.
+ * fx_set_obstacles: replaces the previous mask; NULL detaches (`bytes` is ignored): every call behaves exactly as without this function.  An
+ * all-zero mask is legal and keeps the obstacle kernels in force.  flags & FX_OBSTACLES_DEVICE: `solid` is device memory of the context's
+ * device, read by work enqueued on `stream` during this call only; otherwise host memory.  The call returns once the mask has been read;
+ * set it on the stream the steps run on (or synchronise in between).  FX_E_INVALID, the previous mask staying in force, for bytes != X * Y * Z,
+ * unknown flag bits, a context that owns fewer planes than the grid (slab ranks of every transport, on the same footing as the confinement)
+ * and FX_JACOBI_FAITHFUL contexts (the per-cell freeze solve with obstacles is out of scope: its sparse solver has no obstacle-aware kernels);
+ * FX_E_STATE for FX_FLAG_RENDER_ONLY; FX_E_NOMEM if the code volume cannot be allocated.
+ * fx_get_obstacles: the mask in force as 0 / 1 per cell (all 0 when none) and the count of solid cells; either out may be NULL; blocks like
+ * fx_download.  FX_E_INVALID for bytes != X * Y * Z with solid_out set.
+ * Configuration like the confinement and the emitters: per context, kept across fx_update_frame, not checkpointed (set it again after
+ * fx_checkpoint_load), not part of fx_field_digest.
+ * fx_enforce_obstacles: the enforce stage alone, beside fx_emit, with the time step of the last fx_update_frame; nothing (FX_OK) with no
+ * obstacles or dt <= 0.  fx_divergence / fx_jacobi / fx_project take the obstacle kernels while a mask is set.
+ * Timing: the enforce pass is booked into fx_timing.advect_ms; jacobi_launches = jacobi_sweeps with a mask. */
+#define FX_OBSTACLES_DEVICE 0x1u
+int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t bytes, uint32_t flags);
+int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells);
+int fx_enforce_obstacles(fx_ctx* ctx, void* stream);
+
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
 int fx_sh_transform(fx_ctx* ctx, const float* cube, uint32_t n, float* out27);
