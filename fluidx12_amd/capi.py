@@ -21,10 +21,12 @@ OPT_OVERLAP, OPT_JACOBI_ROUND, OPT_ADAPTIVE_HALO, OPT_COUNT_SAMPLES, OPT_RENDER_
 ABI_VERSION = 7                      # FX_ABI_VERSION of include/fluidx_hip.h
 (FIELD_VELOCITY, FIELD_VELOCITY1, FIELD_COLOR, FIELD_COLOR_PREV, FIELD_PRESSURE, FIELD_DIVERGENCE,
  FIELD_LIGHTMAP, FIELD_CUBEMAP, FIELD_TARGET, FIELD_TARGET_FLOAT, FIELD_CUBE_DEPTH) = range(11)
+FIELD_TEMPERATURE = 11               # FX_FIELD_TEMPERATURE: float[Z][Y][X], only while fx_set_buoyancy has it on
 DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is device memory, read in place
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
 OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memory
+MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
 
 
 class Desc(C.Structure):
@@ -49,6 +51,15 @@ class Light(C.Structure):
 class Emitter(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_float),
                 ("color_rate", C.c_float * 4), ("force", C.c_float * 3), ("swirl", C.c_float)]
+
+
+class Buoyancy(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("ambient", C.c_float), ("density_weight", C.c_float),
+                ("lift", C.c_float), ("cooling", C.c_float), ("up", C.c_float * 3)]
+
+
+class HeatSource(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_float), ("rate", C.c_float)]
 
 
 class Timing(C.Structure):
@@ -97,6 +108,11 @@ SYMBOLS = {
     "fx_set_obstacles": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32]),
     "fx_get_obstacles": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     "fx_enforce_obstacles": (C.c_int, [_vp, _vp]),
+    "fx_set_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy)]),
+    "fx_get_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy), C.POINTER(C.c_int)]),
+    "fx_set_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32]),
+    "fx_get_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fx_heat": (C.c_int, [_vp, _vp]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),

@@ -146,6 +146,34 @@ public:
 	// the enforce stage alone (fx_enforce_obstacles), beside Emit
 	bool EnforceObstacles(void* stream = nullptr) { m_status = fx_enforce_obstacles(m_ctx, stream); return m_status == FX_OK; }
 
+	// not in the reference (its only lift is the constant force inside its impulse ball): buoyancy -- a temperature advected with the flow that
+	// lifts the smoke, and the smoke's weight (fx_set_buoyancy; nullptr = off, the default) --, its heat sources (fx_set_heat_sources) and the
+	// stage alone (fx_heat), beside Emit.  The field is FX_FIELD_TEMPERATURE while buoyancy is on
+	bool SetBuoyancy(const fx_buoyancy* buoyancy) { m_status = fx_set_buoyancy(m_ctx, buoyancy); return m_status == FX_OK; }
+	bool SetBuoyancy(float ambient, float densityWeight, float lift, float cooling, float upX = 0.0f, float upY = 1.0f, float upZ = 0.0f)
+	{
+		const fx_buoyancy b = { (uint32_t)sizeof(fx_buoyancy), 0u, ambient, densityWeight, lift, cooling, { upX, upY, upZ } };
+		return SetBuoyancy(&b);
+	}
+	bool GetBuoyancy(fx_buoyancy& out, bool& enabled)
+	{
+		int on = 0;
+		m_status = fx_get_buoyancy(m_ctx, &out, &on);
+		enabled = on != 0;
+		return m_status == FX_OK;
+	}
+	bool SetHeatSources(const fx_heat_source* list, uint32_t count) { m_status = fx_set_heat_sources(m_ctx, list, count); return m_status == FX_OK; }
+	bool SetHeatSources(const std::vector<fx_heat_source>& list) { return SetHeatSources(list.data(), (uint32_t)list.size()); }
+	bool GetHeatSources(std::vector<fx_heat_source>& out)
+	{
+		uint32_t n = 0;
+		out.resize(FX_MAX_HEAT_SOURCES);
+		m_status = fx_get_heat_sources(m_ctx, out.data(), FX_MAX_HEAT_SOURCES, &n);
+		out.resize(m_status == FX_OK ? n : 0);
+		return m_status == FX_OK;
+	}
+	bool Heat(void* stream = nullptr) { m_status = fx_heat(m_ctx, stream); return m_status == FX_OK; }
+
 	// not in the reference (its state dies with the window): whole-grid state files, see fx_checkpoint_save
 	bool SaveCheckpoint(const char* path) { m_status = fx_checkpoint_save(m_ctx, path); return m_status == FX_OK; }
 	bool LoadCheckpoint(const char* path) { m_status = fx_checkpoint_load(m_ctx, path); return m_status == FX_OK; }

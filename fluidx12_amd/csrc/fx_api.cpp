@@ -530,6 +530,95 @@ int fx_enforce_obstacles(fx_ctx* ctx, void* stream)
 	return enforce_phase(ctx, pick_stream(ctx, stream));
 }
 
+// ---- buoyancy (fx_heat.hip) -------------------------------------------------------------------------------
+int fx_set_buoyancy(fx_ctx* ctx, const fx_buoyancy* b)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the confinement's footing (the field would need halo planes of its own)
+	DeviceGuard dg(ctx->device);
+	if (!b) {                                                               // off: every call behaves as without this function, the field goes
+		for (int i = 0; i < 2; ++i) {
+			if (ctx->temp[i]) FX_HIP(hipFree(ctx->temp[i]));                // (hipFree waits for the device: nothing reads the volume any more)
+			ctx->temp[i] = nullptr;
+		}
+		ctx->temp_cur = 0;
+		ctx->buoy_on = false;
+		const fx_buoyancy off = { (uint32_t)sizeof(fx_buoyancy), 0u, 0.0f, 0.0f, 0.0f, 0.0f, { 0.0f, 1.0f, 0.0f } };
+		ctx->buoy = off;
+		return FX_OK;
+	}
+	if (b->struct_size != sizeof(fx_buoyancy) || b->flags != 0) return FX_E_INVALID;
+	if (!std::isfinite(b->ambient) || !std::isfinite(b->density_weight) || !std::isfinite(b->lift) || !std::isfinite(b->cooling)) return FX_E_INVALID;
+	if (b->density_weight < 0.0f || b->cooling < 0.0f) return FX_E_INVALID;
+	for (int a = 0; a < 3; ++a) if (!std::isfinite(b->up[a])) return FX_E_INVALID;
+	if (b->up[0] == 0.0f && b->up[1] == 0.0f && b->up[2] == 0.0f) return FX_E_INVALID;
+	if (!ctx->temp[0]) {                                                    // the first successful call: the ping-pong pair, both at the ambient value
+		const size_t n = ctx->g.cells_owned();
+		float* t[2] = { nullptr, nullptr };
+		for (int i = 0; i < 2; ++i)
+			if (hipMalloc((void**)&t[i], n * sizeof(float)) != hipSuccess) {
+				(void)hipGetLastError();
+				if (t[0]) (void)hipFree(t[0]);
+				return FX_E_NOMEM;
+			}
+		uint32_t bits;
+		std::memcpy(&bits, &b->ambient, sizeof bits);
+		hipError_t e = hipMemsetD32Async((hipDeviceptr_t)t[0], (int)bits, n, ctx->stream);
+		if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)t[1], (int)bits, n, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t[0]); (void)hipFree(t[1]); return FX_E_DEVICE; }
+		ctx->temp[0] = t[0]; ctx->temp[1] = t[1];
+		ctx->temp_cur = 0;
+	}
+	ctx->buoy = *b;
+	ctx->buoy_on = true;
+	return FX_OK;
+}
+
+int fx_get_buoyancy(fx_ctx* ctx, fx_buoyancy* out, int* enabled)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (out) *out = ctx->buoy;
+	if (enabled) *enabled = ctx->buoy_on ? 1 : 0;
+	return FX_OK;
+}
+
+int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (count > FX_MAX_HEAT_SOURCES || (count && !list)) return FX_E_INVALID;
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;
+	for (uint32_t k = 0; k < count; ++k) {
+		const fx_heat_source& e = list[k];
+		if (e.struct_size != sizeof(fx_heat_source) || e.flags != 0) return FX_E_INVALID;
+		if (!std::isfinite(e.radius) || !(e.radius > 0.0f) || !std::isfinite(e.rate)) return FX_E_INVALID;
+		for (int a = 0; a < 3; ++a) if (!std::isfinite(e.center[a])) return FX_E_INVALID;
+	}
+	ctx->heat_sources.assign(list, list + count);
+	return FX_OK;
+}
+
+int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uint32_t* count)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (!count || (capacity && !out)) return FX_E_INVALID;
+	*count = (uint32_t)ctx->heat_sources.size();
+	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->heat_sources[k];
+	return FX_OK;
+}
+
+int fx_heat(fx_ctx* ctx, void* stream)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	return heat_phase(ctx, pick_stream(ctx, stream));
+}
+
 int fx_divergence(fx_ctx* ctx, void* stream)
 {
 	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;

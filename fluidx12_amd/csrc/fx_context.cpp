@@ -96,7 +96,7 @@ void free_all(fx_ctx* c)
 		if (c->p[i]) (void)hipFree(c->p[i]);
 	}
 	void* others[] = { c->env, c->cube_depth, c->depth_own, c->accel.occ, c->accel.alpha, c->accel.bits, c->accel.list, c->accel.cells, c->accel.gi, c->accel.ctr, c->target, c->target_float, c->p_face[0], c->p_face[1], c->b, c->frozen, c->frozen_alt, c->lightmap, c->cube, c->sh_dev, c->halo_overflow, c->stage,
-		c->sh_scratch[0], c->sh_scratch[1], c->sh_scratch[2], c->sh_scratch[3], c->p_aux, c->fz_mask[0], c->fz_mask[1], c->fz_mask[2], c->fz_tile_next, c->fz_stat, c->fz_list[0], c->fz_list[1], c->fz_counts, c->sample_counters, c->adv_far, c->obst_code, c->obst_spare, c->obst_stats };
+		c->sh_scratch[0], c->sh_scratch[1], c->sh_scratch[2], c->sh_scratch[3], c->p_aux, c->fz_mask[0], c->fz_mask[1], c->fz_mask[2], c->fz_tile_next, c->fz_stat, c->fz_list[0], c->fz_list[1], c->fz_counts, c->sample_counters, c->adv_far, c->obst_code, c->obst_spare, c->obst_stats, c->temp[0], c->temp[1] };
 	for (void* q : others) if (q) (void)hipFree(q);
 	for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
 	if (c->step_rec) (void)hipFree(c->step_rec);
@@ -378,6 +378,7 @@ static int field_info(fx_ctx* c, int field, size_t* host_bytes)
 	case FX_FIELD_COLOR: *host_bytes = 4 * n * 4; return FX_OK;
 	case FX_FIELD_PRESSURE: case FX_FIELD_DIVERGENCE: if (!c->b) return FX_E_STATE; *host_bytes = n * 4; return FX_OK;
 	case FX_FIELD_LIGHTMAP: if (!c->lightmap) return FX_E_INVALID; *host_bytes = 3 * n * 4; return FX_OK;
+	case FX_FIELD_TEMPERATURE: if (!c->buoy_on || !c->temp[0]) return FX_E_STATE; *host_bytes = n * 4; return FX_OK;   // only while fx_set_buoyancy has it on
 	case FX_FIELD_CUBEMAP: {
 		if (!c->cube) return FX_E_INVALID;
 		const size_t s = (size_t)c->g.X >> c->cube_lod;
@@ -455,7 +456,8 @@ int fx_upload(fx_ctx* ctx, int field, const void* host, size_t bytes)
 	// a state that comes from outside (a test's fields, a checkpoint): what the sparse solver had learnt about the OLD state's relaxing
 	// tiles -- how many masked strip launches a solve takes, a count still on its way -- starts over, so that the launch sequence is a
 	// function of (the uploaded state, the steps since) on every run
-	if (field <= FX_FIELD_DIVERGENCE) { ctx->fz_dense_n = 0; ctx->fz_active_pending = false; }
+	// (the buoyancy's temperature is such a state too: it drives the next steps' velocity)
+	if (field <= FX_FIELD_DIVERGENCE || field == FX_FIELD_TEMPERATURE) { ctx->fz_dense_n = 0; ctx->fz_active_pending = false; }
 	const size_t n = ctx->g.cells_owned(), off = (size_t)ctx->g.H * ctx->g.plane(), cl = ctx->g.cells_local();
 	const size_t es = elem_size(ctx);
 	switch (field) {
@@ -496,6 +498,9 @@ int fx_upload(fx_ctx* ctx, int field, const void* host, size_t bytes)
 		break;
 	case FX_FIELD_DIVERGENCE:
 		FX_HIP(hipMemcpy(ctx->b + off, host, need, hipMemcpyHostToDevice));
+		break;
+	case FX_FIELD_TEMPERATURE:   // (whole-grid contexts only: no halo planes)
+		FX_HIP(hipMemcpy(ctx->temp[ctx->temp_cur], host, need, hipMemcpyHostToDevice));
 		break;
 	case FX_FIELD_CUBEMAP:       // mip `cube_lod`: lets the resolve be driven with a known cube map (parity tests, replays)
 		FX_HIP(hipMemcpy(ctx->cube + ctx->cube_mip_offset[ctx->cube_lod], host, need, hipMemcpyHostToDevice));
@@ -543,6 +548,9 @@ int fx_download(fx_ctx* ctx, int field, void* host, size_t bytes)
 		break;
 	case FX_FIELD_DIVERGENCE:
 		FX_HIP(hipMemcpy(host, ctx->b + off, need, hipMemcpyDeviceToHost));
+		break;
+	case FX_FIELD_TEMPERATURE:
+		FX_HIP(hipMemcpy(host, ctx->temp[ctx->temp_cur], need, hipMemcpyDeviceToHost));
 		break;
 	case FX_FIELD_LIGHTMAP:
 		if ((rc = ensure_stage(ctx, need))) return rc;

@@ -69,6 +69,13 @@ struct fx_ctx {
 	unsigned* obst_stats = nullptr; // device, 8 words: what k_obstacle_codes counts
 	uint64_t obst_cells = 0;        // solid cells
 	int obst_lo[3] = { 0, 0, 0 }, obst_hi[3] = { 0, 0, 0 };   // their bounding box [lo, hi): what the enforce launch covers
+	// buoyancy (fx_set_buoyancy / fx_set_heat_sources; configuration on the same terms): the temperature ping-pong pair, fp32 whatever the storage,
+	// allocated by the first fx_set_buoyancy and freed when the feature is switched off (fx_heat.hip: k_heat reads temp[temp_cur], writes the other)
+	bool buoy_on = false;
+	fx_buoyancy buoy = { (uint32_t)sizeof(fx_buoyancy), 0u, 0.0f, 0.0f, 0.0f, 0.0f, { 0.0f, 1.0f, 0.0f } };   // the defaults while off
+	float* temp[2] = { nullptr, nullptr };
+	int temp_cur = 0;
+	std::vector<fx_heat_source> heat_sources;   // may be set while buoyancy is off; empty = none (default)
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -100,6 +100,7 @@ int options_digest(const fx_ctx* c);
 int advect_range(fx_ctx* ctx, hipStream_t s, Range r, bool own_only);   // planes [r.lo, r.hi); own_only: back-traces must stay inside the owned planes
 int advect_all(fx_ctx* ctx, std::vector<fx_ctx*>& M, hipStream_t s);
 int emit_phase(fx_ctx* ctx, hipStream_t s);          // the settable emitters on velocity[1] / colour[parity]; nothing with an empty list or dt <= 0
+int heat_phase(fx_ctx* ctx, hipStream_t s);          // buoyancy: the temperature advected / cooled / heated, the force on velocity[1]; nothing while it is off or with dt <= 0
 int enforce_phase(fx_ctx* ctx, hipStream_t s);       // the solid cells of velocity[1] / colour[parity] become +0; nothing without solid cells or with dt <= 0
 int confine_phase(fx_ctx* ctx, hipStream_t s);       // vorticity confinement of velocity[1]; nothing with epsilon = 0 or dt <= 0
 int divergence_phase(fx_ctx* ctx, hipStream_t s);

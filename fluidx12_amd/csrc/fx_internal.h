@@ -82,6 +82,17 @@ struct EmitBall { float c[3], rr, rate[4], force[3], swirl; int lo[3], hi[3]; };
 struct EmitArgs { int n, x0, y0, z0, tiles_x, tiles_y, tiles_z; EmitBall e[FX_MAX_EMITTERS]; };
 int emit_plan(const Geom& g, const fx_emitter* list, int count, EmitArgs* out);
 hipError_t launch_emit(const Geom& g, int half_store, void* vel, void* col, float* alpha, const fx_emitter* list, int count, float dt, hipStream_t s);
+// buoyancy (fx_heat.hip), one launch over a whole grid: the temperature t_in is advected with vel0, cooled, heated by the sources and stored
+// to t_out; VELOCITY1 (vel1) gets the force, in place, on the axes with up != 0; hipErrorNotSupported for a slab geometry.  code: the
+// obstacle bytes (fx_obstacle.hip) or null.  HeatArgs is what the kernel gets: the coefficients, the axes the force acts on (bit a: up[a] != 0,
+// never z on a 2-D grid), the grid's 64 x 4 raster and the sources whose clipped bounding box [lo, hi) holds a cell, in list order.
+// heat_plan (fx_heat_plan.cpp; host code, no device needed: it takes the boxes from emit_plan) fills it -> workgroups to launch (below 0: too many)
+const int kHeatTileX = 64, kHeatTileY = 4;
+struct HeatBall { float c[3], rr, rate; int lo[3], hi[3]; };
+struct HeatArgs { float ambient, weight, lift, cooling, up[3]; int axes, n, tiles_x, tiles_y; HeatBall s[FX_MAX_HEAT_SOURCES]; };
+int heat_plan(const Geom& g, const fx_buoyancy& b, const fx_heat_source* list, int count, HeatArgs* out);
+hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
+	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
 // ---- solid obstacles (fx_obstacle.hip), whole grids only (hipErrorNotSupported for a slab geometry).  code: one byte per cell, bits 0..5 = the
 // clamped neighbour at x-1, x+1, y-1, y+1, z-1, z+1 is solid (z bits 0 on 2-D grids), bit 6 = the cell is; the stencil launchers read it, never the mask

@@ -311,6 +311,22 @@ int emit_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// Buoyancy (fx_heat.hip): behind the emitters -- the force reads the alpha they have added to --, in front of the enforce pass (the pass skips
+// solid cells itself, the enforce pass clears their velocity as always) and of the confinement, which leaves velocity[0] unspecified: the
+// temperature is traced with velocity[0], the field this step's advection traced with.  One launch over the grid, temp[temp_cur] -> the
+// other buffer, then the two swap; the force goes into velocity[1] in place.  Booked with the advection like its neighbours.
+int heat_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->buoy_on || !ctx->temp[0] || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	const int cur = ctx->temp_cur;
+	FX_HIP(launch_heat(ctx->g, ctx->half, ctx->buoy, ctx->heat_sources.data(), (int)ctx->heat_sources.size(), ctx->vel[0], ctx->vel[1],
+		ctx->col[ctx->frame_parity], ctx->temp[cur], ctx->temp[1 - cur], ctx->obst_code, ctx->time_step, (int)ctx->desc.advect_address, s));
+	ctx->temp_cur = 1 - cur;
+	return FX_OK;
+}
+
 // Solid obstacles (fx_obstacle.hip): behind the advection and the emitters, in front of the confinement, the solid cells of the advected velocity
 // and colour become +0, in place -- one launch over the solids' bounding box, booked with the advection like the two passes around it.  When this
 // step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well (the emitters' condition).
@@ -699,6 +715,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
 		for (fx_ctx* m : M) if ((rc = emit_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with emitters set only)
+		for (fx_ctx* m : M) if ((rc = heat_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with buoyancy on only)
 		for (fx_ctx* m : M) if ((rc = enforce_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with obstacles set only)
 		for (fx_ctx* m : M) if ((rc = confine_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with epsilon > 0 only)
 		const ExchSpec uz{ EX_UZ1, 1, 0 };

@@ -335,6 +335,61 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_enforce_obstacles(self._ctx, stream), "EnforceObstacles")
 
+    def SetBuoyancy(self, ambient=0.0, density_weight=0.0, lift=0.0, cooling=0.0, up=(0.0, 1.0, 0.0), flags=0):
+        """buoyancy (fx_set_buoyancy): a temperature field advected with the flow, cooling towards `ambient` by max(1 - cooling * dt, 0) per step,
+        and the force (-density_weight * COLOR.w + lift * (T - ambient)) * up on VELOCITY1, one pass behind the emitters.  `up` is used as given.
+        SetBuoyancy(None) switches it off (default) and frees the field; the first call that switches it on fills the field with `ambient`, a
+        later one replaces the coefficients and keeps it.  The field is FIELD_TEMPERATURE (upload / download while on).  Configuration: kept
+        across UpdateFrame, not stored in checkpoints (set it again and upload the temperature after LoadCheckpoint).  Whole-grid contexts only."""
+        self._need()
+        if ambient is None:
+            capi.check(self._lib.fx_set_buoyancy(self._ctx, None), "SetBuoyancy")
+            return
+        b = capi.Buoyancy()
+        b.struct_size, b.flags = C.sizeof(capi.Buoyancy), int(flags)
+        b.ambient, b.density_weight, b.lift, b.cooling = float(ambient), float(density_weight), float(lift), float(cooling)
+        b.up = (C.c_float * 3)(*[float(v) for v in up])
+        capi.check(self._lib.fx_set_buoyancy(self._ctx, C.byref(b)), "SetBuoyancy")
+
+    def GetBuoyancy(self):
+        """the coefficients in force (fx_get_buoyancy) as a dict with SetBuoyancy's keys, or None while buoyancy is off"""
+        self._need()
+        b, on = capi.Buoyancy(), C.c_int(0)
+        capi.check(self._lib.fx_get_buoyancy(self._ctx, C.byref(b), C.byref(on)), "GetBuoyancy")
+        if not on.value:
+            return None
+        return {"ambient": b.ambient, "density_weight": b.density_weight, "lift": b.lift, "cooling": b.cooling, "up": tuple(b.up), "flags": b.flags}
+
+    def SetHeatSources(self, sources):
+        """the heat sources of the buoyancy pass (fx_set_heat_sources): a sequence of dicts (or capi.HeatSource) with "center" (x, y, z) and "radius"
+        as an emitter's, and "rate" (temperature per unit time at the centre; negative = a cold source).  None or () = none (default).  May be
+        set while buoyancy is off.  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid contexts only."""
+        self._need()
+        items = list(sources or ())
+        arr = (capi.HeatSource * max(len(items), 1))()
+        for k, e in enumerate(items):
+            if isinstance(e, capi.HeatSource):
+                arr[k] = e
+                continue
+            arr[k].struct_size, arr[k].flags = C.sizeof(capi.HeatSource), int(e.get("flags", 0))
+            arr[k].center = (C.c_float * 3)(*[float(v) for v in e["center"]])
+            arr[k].radius = float(e["radius"])
+            arr[k].rate = float(e["rate"])
+        capi.check(self._lib.fx_set_heat_sources(self._ctx, arr if items else None, len(items)), "SetHeatSources")
+
+    def GetHeatSources(self):
+        """the list in force (fx_get_heat_sources), as dicts with the keys SetHeatSources takes"""
+        self._need()
+        n = C.c_uint32(0)
+        arr = (capi.HeatSource * capi.MAX_HEAT_SOURCES)()
+        capi.check(self._lib.fx_get_heat_sources(self._ctx, arr, capi.MAX_HEAT_SOURCES, C.byref(n)), "GetHeatSources")
+        return [{"center": tuple(e.center), "radius": e.radius, "rate": e.rate, "flags": e.flags} for e in arr[:n.value]]
+
+    def Heat(self, stream=None):
+        """the buoyancy stage alone (fx_heat): TEMPERATURE advected with VELOCITY, the force in place on VELOCITY1; run it before ConfineVorticity"""
+        self._need()
+        capi.check(self._lib.fx_heat(self._ctx, stream), "Heat")
+
     def Divergence(self, stream=None):
         capi.check(self._lib.fx_divergence(self._ctx, stream), "Divergence")
 
@@ -357,7 +412,7 @@ class Fluid:
             return (3, nz, Y, X), np.float32
         if field in (capi.FIELD_COLOR, capi.FIELD_COLOR_PREV):
             return (nz, Y, X, 4), np.float32
-        if field in (capi.FIELD_PRESSURE, capi.FIELD_DIVERGENCE):
+        if field in (capi.FIELD_PRESSURE, capi.FIELD_DIVERGENCE, capi.FIELD_TEMPERATURE):
             return (nz, Y, X), np.float32
         if field == capi.FIELD_LIGHTMAP:
             return (nz, Y, X, 3), np.float32

@@ -59,13 +59,15 @@ enum fx_address { FX_ADDRESS_CLAMP = 0,         /* FluidEZ.cpp:406 (default path
  *   CUBEMAP   uint8[6][S][S][4]  (mip `lod` of m_cubeMap, S = X >> lod, R8G8B8A8_UNORM)
  *   CUBE_DEPTH float[6][S][S]    (mip `lod` of the cube depth: the scene depth each texel's ray saw when the last cube-path fx_render ran
  *                                with a depth attached, CSRayMarch.hlsl:124; 1.0 where no such ray was cast; download only)
+ *   TEMPERATURE float[Z][Y][X]   (the buoyancy's temperature, fp32 on the device too; only while fx_set_buoyancy has it on, FX_E_STATE otherwise)
  * Z = the context's own slab (slab_nz planes), never the halo. */
 enum fx_field {
 	FX_FIELD_VELOCITY = 0, FX_FIELD_VELOCITY1 = 1, FX_FIELD_COLOR = 2, FX_FIELD_COLOR_PREV = 3,
 	FX_FIELD_PRESSURE = 4, FX_FIELD_DIVERGENCE = 5, FX_FIELD_LIGHTMAP = 6, FX_FIELD_CUBEMAP = 7,
 	FX_FIELD_TARGET = 8,        /* render target of fx_render_cube: uint8 [viewport_h][viewport_w][4] (download only) */
 	FX_FIELD_TARGET_FLOAT = 9,  /* the resolve's output before the blend: float [h][w][4], zeros where discarded     */
-	FX_FIELD_CUBE_DEPTH = 10    /* see above (3-D contexts with a viewport)                                          */
+	FX_FIELD_CUBE_DEPTH = 10,   /* see above (3-D contexts with a viewport)                                          */
+	FX_FIELD_TEMPERATURE = 11   /* see above and fx_set_buoyancy                                                     */
 };
 
 typedef struct fx_ctx fx_ctx;
@@ -365,6 +367,62 @@ int fx_emit(fx_ctx* ctx, void* stream);
 int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t bytes, uint32_t flags);
 int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells);
 int fx_enforce_obstacles(fx_ctx* ctx, void* stream);
+
+/* Buoyancy (Fedkiw, Stam, Jensen 2001, eq. 8; no reference counterpart -- the reference's only lift is the constant force inside its impulse
+ * ball): a temperature T that is advected with the flow, cools towards an ambient value and, with the smoke density rho = COLOR.w, pushes
+ * the velocity along `up`:   f = (-density_weight * rho + lift * (T - ambient)) * up.   With buoyancy on, fx_simulate runs one more pass
+ * (one launch over the grid) behind the emitters and in front of the obstacle enforce pass, the confinement and the divergence:
+ * advect -> emit -> heat -> enforce -> confine -> divergence ...   Per cell (x, y, z), fp32, every operation rounded as written
+ * (tests/buoyancy_ref.py restates it in numpy), u0 = VELOCITY (the velocity the step's advection traced with), Ta = ambient:
+ *   1  p = ((x + .5) / X, (y + .5) / Y, (z + .5) / Z)      a = fma(-u0, dt, p)      t = a * N - 0.5, i0 = floor(t), f = t - i0 per axis;
+ *      the eight taps i0, i0 + 1 go through the context's address mode (clamp / mirror), Ts = lerp_z(lerp_y(lerp_x ...)) with
+ *      lerp(a, b, f) = fma(f, b - a, a): the back-trace and the sampler of the colour advection, tap for tap (2-D grids: both z taps are plane 0)
+ *   2  T1 = fma(Ts - Ta, max(fma(-dt, cooling, 1), 0), Ta)
+ *   3  for every heat source e in list order: basis as an emitter forms it (d = p - e.center, 2-D grids: dz = 0,
+ *      basis = exp2(((d2 * -4) / (radius * radius)) * 1.44269502));   if (basis >= e^-4) T1 = fma(basis * dt, e.rate, T1)      -- no clamp
+ *   4  a solid cell (fx_set_obstacles) gets T1 = Ta and its velocity is left alone (the enforce pass behind clears it)
+ *   5  T1 is stored into the second temperature buffer and the two swap
+ *   6  fluid cells: s = fma(lift, T1 - Ta, -(density_weight * rho)), rho = COLOR.w as stored (what the emitters added included), and for
+ *      each axis a with up[a] != 0 (2-D grids: never z):   VELOCITY1[a] = fma(up[a] * s, dt, VELOCITY1[a]);   a component with up[a] == 0
+ *      is neither read nor written.  fp16 storage widens on load and rounds the stored component once (RNE).
+ * The field: the first successful fx_set_buoyancy allocates two fp32 volumes of X * Y * Z (fp32 whatever fx_desc.storage is), both filled
+ * with `ambient`; FX_E_NOMEM if that fails.  A later call replaces the coefficients and keeps the field; NULL switches the feature off (the
+ * default: every call behaves exactly as without this function) and frees the field.  While buoyancy is on, fx_upload / fx_download /
+ * fx_field_bytes serve FX_FIELD_TEMPERATURE; while it is off they return FX_E_STATE (fx_field_bytes: 0).  fx_field_digest does not take it.
+ * Configuration like the emitters: per context, kept across fx_update_frame, not part of fx_field_digest.  The checkpoint file does not hold
+ * the temperature: a caller who resumes calls fx_set_buoyancy (and fx_set_heat_sources) again behind fx_checkpoint_load and uploads the
+ * FX_FIELD_TEMPERATURE they downloaded when they saved; the run then continues bit-identically.
+ * fx_set_heat_sources: count 0 (list may be NULL) = none, the default.  The list may be set while buoyancy is off and takes effect once it
+ * is on.  It travels with the launch like the emitters (no device memory, no copy).  A cold source (rate < 0) is legal.
+ * FX_E_INVALID, the previous setting staying in force: a wrong struct_size, unknown flag bits, a non-finite member, a negative
+ * density_weight or cooling, `up` all zero, radius <= 0, count > FX_MAX_HEAT_SOURCES, and (both setters, fx_heat) a context that owns fewer
+ * planes than the grid -- slab ranks of every transport, on the same footing as the confinement: the field would need halo planes of its
+ * own.  FX_E_STATE (all five calls): FX_FLAG_RENDER_ONLY contexts.  Both Jacobi modes, 2-D grids, both address modes and obstacles are served.
+ * fx_get_buoyancy: *enabled gets 0 / 1 and *out the coefficients in force (the defaults while off); either may be NULL.
+ * fx_get_heat_sources: as fx_get_emitters.
+ * fx_heat: the stage alone, beside fx_emit, with the time step of the last fx_update_frame; nothing (FX_OK) while buoyancy is off or
+ * dt <= 0.  It reads FX_FIELD_VELOCITY, so it must run BEFORE fx_confine_vorticity, which leaves that field unspecified.
+ * Timing: booked into fx_timing.advect_ms. */
+#define FX_MAX_HEAT_SOURCES 16u
+typedef struct fx_buoyancy {
+	uint32_t struct_size, flags;   /* flags: 0 (unknown bits: FX_E_INVALID) */
+	float ambient;                 /* T_amb; the field starts at this value everywhere */
+	float density_weight;          /* alpha >= 0: pulls smoke (COLOR.w) down along -up */
+	float lift;                    /* beta: pushes (T - T_amb) along up; any finite value */
+	float cooling;                 /* >= 0, per unit time: T relaxes to ambient by max(1 - cooling * dt, 0) per step */
+	float up[3];                   /* direction of "up" in grid axes, used as given (not normalised); default (0, 1, 0) */
+} fx_buoyancy;
+typedef struct fx_heat_source {
+	uint32_t struct_size, flags;   /* flags: 0 (unknown bits: FX_E_INVALID) */
+	float center[3];               /* texture space, as fx_emitter.center */
+	float radius;                  /* > 0, as fx_emitter.radius */
+	float rate;                    /* temperature per unit time at the centre; any finite value */
+} fx_heat_source;
+int fx_set_buoyancy(fx_ctx* ctx, const fx_buoyancy* buoyancy);
+int fx_get_buoyancy(fx_ctx* ctx, fx_buoyancy* out, int* enabled);
+int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count);
+int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uint32_t* count);
+int fx_heat(fx_ctx* ctx, void* stream);
 
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
