@@ -27,6 +27,8 @@ LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
 OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memory
 MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
+WALL_X_LO, WALL_X_HI, WALL_Y_LO, WALL_Y_HI, WALL_Z_LO, WALL_Z_HI = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20   # FX_WALL_*: fx_set_open_walls
+WALL_ALL = 0x3F
 
 
 class Desc(C.Structure):
@@ -113,6 +115,9 @@ SYMBOLS = {
     "fx_set_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32]),
     "fx_get_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32, C.POINTER(C.c_uint32)]),
     "fx_heat": (C.c_int, [_vp, _vp]),
+    "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
+    "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "fx_open_inflow": (C.c_int, [_vp, _vp]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),

@@ -146,6 +146,12 @@ public:
 	// the enforce stage alone (fx_enforce_obstacles), beside Emit
 	bool EnforceObstacles(void* stream = nullptr) { m_status = fx_enforce_obstacles(m_ctx, stream); return m_status == FX_OK; }
 
+	// not in the reference (its box is closed): the faces through which the smoke leaves (fx_set_open_walls; FX_WALL_* bits, 0 = all closed,
+	// the default) and the inflow stage alone (fx_open_inflow), directly behind the advection, beside Emit
+	bool SetOpenWalls(uint32_t faces) { m_status = fx_set_open_walls(m_ctx, faces); return m_status == FX_OK; }
+	bool GetOpenWalls(uint32_t& faces) { m_status = fx_get_open_walls(m_ctx, &faces); return m_status == FX_OK; }
+	bool OpenInflow(void* stream = nullptr) { m_status = fx_open_inflow(m_ctx, stream); return m_status == FX_OK; }
+
 	// not in the reference (its only lift is the constant force inside its impulse ball): buoyancy -- a temperature advected with the flow that
 	// lifts the smoke, and the smoke's weight (fx_set_buoyancy; nullptr = off, the default) --, its heat sources (fx_set_heat_sources) and the
 	// stage alone (fx_heat), beside Emit.  The field is FX_FIELD_TEMPERATURE while buoyancy is on

@@ -530,6 +530,35 @@ int fx_enforce_obstacles(fx_ctx* ctx, void* stream)
 	return enforce_phase(ctx, pick_stream(ctx, stream));
 }
 
+// ---- open walls (fx_open.hip) ---------------------------------------------------------------------------
+int fx_set_open_walls(fx_ctx* ctx, uint32_t faces)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (faces & ~0x3Fu) return FX_E_INVALID;
+	if (ctx->g.Zg <= 1 && (faces & (FX_WALL_Z_LO | FX_WALL_Z_HI))) return FX_E_INVALID;   // a 2-D grid has no z faces
+	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the obstacles' footing
+	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no open-wall kernels
+	ctx->open_faces = faces;
+	return FX_OK;
+}
+
+int fx_get_open_walls(fx_ctx* ctx, uint32_t* faces)
+{
+	if (!ctx || !faces) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	*faces = ctx->open_faces;
+	return FX_OK;
+}
+
+int fx_open_inflow(fx_ctx* ctx, void* stream)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
+	return open_inflow_phase(ctx, pick_stream(ctx, stream));
+}
+
 // ---- buoyancy (fx_heat.hip) -------------------------------------------------------------------------------
 int fx_set_buoyancy(fx_ctx* ctx, const fx_buoyancy* b)
 {

@@ -69,6 +69,8 @@ struct fx_ctx {
 	unsigned* obst_stats = nullptr; // device, 8 words: what k_obstacle_codes counts
 	uint64_t obst_cells = 0;        // solid cells
 	int obst_lo[3] = { 0, 0, 0 }, obst_hi[3] = { 0, 0, 0 };   // their bounding box [lo, hi): what the enforce launch covers
+	// open walls (fx_set_open_walls; configuration on the same terms): FX_WALL_* bits, 0 = all six faces closed: every launch is today's
+	uint32_t open_faces = 0;
 	// buoyancy (fx_set_buoyancy / fx_set_heat_sources; configuration on the same terms): the temperature ping-pong pair, fp32 whatever the storage,
 	// allocated by the first fx_set_buoyancy and freed when the feature is switched off (fx_heat.hip: k_heat reads temp[temp_cur], writes the other)
 	bool buoy_on = false;

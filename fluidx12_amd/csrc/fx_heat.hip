@@ -7,6 +7,7 @@
 //   px = ((float)x + 0.5f) / (float)X (py, pz alike)      a = fmaf(-u0, dt, p)         u0 = velocity[0], the field k_advect traces with
 //   t = a * N - 0.5f, i0 = floorf(t), f = t - i0          taps i0, i0 + 1 through the address mode (clamp / mirror)
 //   Ts = lerp_z(lerp_y(lerp_x ...)), lerp(a, b, f) = fmaf(f, b - a, a)                 k_advect's colour sample (fx_sim.hip FX_TRI), restated here
+//   open walls (faces != 0, fx_open.hip): Ts = fmaf(w, Ts - Ta, Ta), w = (wx * wy) * wz (2-D: no wz) of open_wall_weight(i0, f) -- a ghost at Ta
 //   T1 = fmaf(Ts - Ta, fmaxf(fmaf(-dt, cooling, 1), 0), Ta)
 //   for each source e in list order: basis as k_emit forms it; if (basis >= e^-4) T1 = fmaf(basis * dt, e.rate, T1)
 //   a solid cell (code bit 6, fx_obstacle.hip): T1 = Ta, nothing else
@@ -70,7 +71,8 @@ __device__ __forceinline__ int addr_tap(int i, int n, int mode)
 
 template <bool HALF, bool IS3D, bool WIDE>
 __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, const void* __restrict__ vel0, void* __restrict__ vel1,
-	const void* __restrict__ col, const float* __restrict__ t_in, float* __restrict__ t_out, const uint8_t* __restrict__ code, float dt, int address)
+	const void* __restrict__ col, const float* __restrict__ t_in, float* __restrict__ t_out, const uint8_t* __restrict__ code, float dt, int address,
+	unsigned faces)
 {
 	typedef Cell<HALF> Ce;
 	typedef typename Off<WIDE>::T O;
@@ -123,6 +125,13 @@ __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, co
 		Ts = lerpf(c, c, fz);
 	}
 
+	// ---- 1b: open walls (fx_open.hip; launch-uniform, 0 = none): the cells beyond an open face are at the ambient value
+	if (faces) {
+		float w = open_wall_weight(flx, fx, g.X, faces & 1u, faces & 2u) * open_wall_weight(fly, fy, g.Y, faces & 4u, faces & 8u);
+		if (IS3D) w = w * open_wall_weight(flz, fz, g.Zg, faces & 16u, faces & 32u);
+		Ts = fmaf(w, Ts - Ta, Ta);
+	}
+
 	// ---- 2: cooling towards the ambient value
 	float T1 = fmaf(Ts - Ta, fmaxf(fmaf(-dt, a.cooling, 1.0f), 0.0f), Ta);
 
@@ -155,28 +164,29 @@ __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, co
 
 template <bool HALF, bool IS3D>
 static hipError_t launch_heat_t(bool wide, dim3 grid, dim3 block, hipStream_t s, const Geom& g, const HeatArgs& a, const void* vel0, void* vel1,
-	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address)
+	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, unsigned faces)
 {
-	if (wide) hipLaunchKernelGGL((k_heat<HALF, IS3D, true>), grid, block, 0, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address);
-	else hipLaunchKernelGGL((k_heat<HALF, IS3D, false>), grid, block, 0, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address);
+	if (wide) hipLaunchKernelGGL((k_heat<HALF, IS3D, true>), grid, block, 0, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces);
+	else hipLaunchKernelGGL((k_heat<HALF, IS3D, false>), grid, block, 0, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces);
 	return hipGetLastError();
 }
 
 hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
-	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s)
+	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s, unsigned faces)
 {
 	if (g.nz != g.Zg || g.H != 0) return hipErrorNotSupported;                  // whole grids only (fx_set_buoyancy refuses slab ranks)
 	if (!vel0 || !vel1 || !col || !t_in || !t_out || t_in == t_out) return hipErrorInvalidValue;
+	if ((faces & ~0x3Fu) || (g.Zg <= 1 && (faces & 0x30u))) return hipErrorInvalidValue;
 	HeatArgs a;
 	const int wgs = heat_plan(g, b, list, count, &a);
 	if (wgs <= 0) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)wgs, 1, 1), block(HT_X, HT_Y, 1);
 	const bool wide = g.cells_local() * 16 >= ((size_t)1 << 32);                // the colour field, the largest one, in fp32
 	const bool is3d = g.Zg > 1;
-	if (half_store) return is3d ? launch_heat_t<true, true>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address)
-	                            : launch_heat_t<true, false>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address);
-	return is3d ? launch_heat_t<false, true>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address)
-	            : launch_heat_t<false, false>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address);
+	if (half_store) return is3d ? launch_heat_t<true, true>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces)
+	                            : launch_heat_t<true, false>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces);
+	return is3d ? launch_heat_t<false, true>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces)
+	            : launch_heat_t<false, false>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces);
 }
 
 }  // namespace fx

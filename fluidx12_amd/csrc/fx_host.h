@@ -99,6 +99,7 @@ int overlap_level(const fx_ctx* lead);
 int options_digest(const fx_ctx* c);
 int advect_range(fx_ctx* ctx, hipStream_t s, Range r, bool own_only);   // planes [r.lo, r.hi); own_only: back-traces must stay inside the owned planes
 int advect_all(fx_ctx* ctx, std::vector<fx_ctx*>& M, hipStream_t s);
+int open_inflow_phase(fx_ctx* ctx, hipStream_t s);   // colour[parity] scaled by the inside share of its back-trace; nothing with all walls closed or dt <= 0
 int emit_phase(fx_ctx* ctx, hipStream_t s);          // the settable emitters on velocity[1] / colour[parity]; nothing with an empty list or dt <= 0
 int heat_phase(fx_ctx* ctx, hipStream_t s);          // buoyancy: the temperature advected / cooled / heated, the force on velocity[1]; nothing while it is off or with dt <= 0
 int enforce_phase(fx_ctx* ctx, hipStream_t s);       // the solid cells of velocity[1] / colour[parity] become +0; nothing without solid cells or with dt <= 0

@@ -91,8 +91,38 @@ const int kHeatTileX = 64, kHeatTileY = 4;
 struct HeatBall { float c[3], rr, rate; int lo[3], hi[3]; };
 struct HeatArgs { float ambient, weight, lift, cooling, up[3]; int axes, n, tiles_x, tiles_y; HeatBall s[FX_MAX_HEAT_SOURCES]; };
 int heat_plan(const Geom& g, const fx_buoyancy& b, const fx_heat_source* list, int count, HeatArgs* out);
+// faces: the open walls (FX_WALL_* bits, 0 = none): the sample is blended towards the ambient value by open_wall_weight of each axis
 hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
-	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s);
+	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s, unsigned faces = 0);
+// ---- open walls (fx_open.hip), whole grids only (hipErrorNotSupported for a slab geometry).  faces: FX_WALL_* bits, the code byte's bit order
+// (x-, x+, y-, y+, z-, z+; no z bit on a 2-D grid: hipErrorInvalidValue); code: the obstacle bytes or null (then no code byte is read)
+// The share of a linear sample at t = i0 + f (i0 = fl = floor(t), taps i0 and i0 + 1 of an axis of n cells) that lies inside the box when the
+// cells beyond an open face are empty: low face open: 0 for i0 < -1, f for i0 == -1; high face open: 0 for i0 >= n, 1 - f for i0 == n - 1; else 1
+__host__ __device__ inline float open_wall_weight(float fl, float f, int n, unsigned lo_open, unsigned hi_open)
+{
+	float w = 1.0f;
+	if (lo_open && fl < 0.0f) w = fl == -1.0f ? f : 0.0f;
+	if (hi_open && fl >= (float)(n - 1)) w = fl == (float)(n - 1) ? 1.0f - f : 0.0f;
+	return w;
+}
+// ... of cell i's back-trace with velocity u0 along that axis, t formed as k_heat (fx_heat.hip) step 1 forms it
+__host__ __device__ inline float open_wall_trace(float u0, float dt, int i, int n, unsigned lo_open, unsigned hi_open)
+{
+	const float p = ((float)i + 0.5f) / (float)n;
+	const float a = fmaf(-u0, dt, p);
+	const float t = a * (float)n - 0.5f;
+	const float fl = floorf(t);
+	return open_wall_weight(fl, t - fl, n, lo_open, hi_open);
+}
+const int kOpenTileX = 64, kOpenTileY = 4;
+bool jacobi_open_takes_v4(const Geom& g);    // 3-D, X % 4 == 0: four cells per thread; else the scalar kernel
+hipError_t launch_jacobi_open(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, unsigned faces,
+	int z_begin, int z_end, hipStream_t s);   // one sweep
+hipError_t launch_project_open(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
+// the inflow pass, in place on a whole-grid colour: COLOR *= w of the back-trace with vel0; alpha: the render's side volume when it holds this
+// colour field's alpha, else null
+hipError_t launch_open_inflow(const Geom& g, int half_store, const void* vel0, void* col, float* alpha, unsigned faces, float dt, hipStream_t s);
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
 // ---- solid obstacles (fx_obstacle.hip), whole grids only (hipErrorNotSupported for a slab geometry).  code: one byte per cell, bits 0..5 = the
 // clamped neighbour at x-1, x+1, y-1, y+1, z-1, z+1 is solid (z bits 0 on 2-D grids), bit 6 = the cell is; the stencil launchers read it, never the mask

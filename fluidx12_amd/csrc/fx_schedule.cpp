@@ -297,6 +297,21 @@ int confine_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// Open walls (fx_open.hip): directly behind the advection and in front of the emitters, the advected colour is scaled by the share of its
+// back-traced sample that lies inside the box -- the cells beyond an open face hold clear air.  The trace is the advection's: velocity[0].
+// One launch over the grid, in place on colour[parity], booked with the advection; it keeps the render's alpha side volume true on the
+// emitters' condition.
+int open_inflow_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->open_faces || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	const int par = ctx->frame_parity;
+	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
+	FX_HIP(launch_open_inflow(ctx->g, ctx->half, ctx->vel[0], ctx->col[par], alpha, ctx->open_faces, ctx->time_step, s));
+	return FX_OK;
+}
+
 // The settable emitters (fx_emit.hip) add to the advected velocity and colour in place, in front of the confinement and of the divergence
 // (the sparse solver's fused one included: it reads velocity[1] behind this launch), booked with the advection like the confinement.
 // When this step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well.
@@ -322,7 +337,7 @@ int heat_phase(fx_ctx* ctx, hipStream_t s)
 	ScopedMark mk(ctx, s, MK_ADVECT);
 	const int cur = ctx->temp_cur;
 	FX_HIP(launch_heat(ctx->g, ctx->half, ctx->buoy, ctx->heat_sources.data(), (int)ctx->heat_sources.size(), ctx->vel[0], ctx->vel[1],
-		ctx->col[ctx->frame_parity], ctx->temp[cur], ctx->temp[1 - cur], ctx->obst_code, ctx->time_step, (int)ctx->desc.advect_address, s));
+		ctx->col[ctx->frame_parity], ctx->temp[cur], ctx->temp[1 - cur], ctx->obst_code, ctx->time_step, (int)ctx->desc.advect_address, s, ctx->open_faces));
 	ctx->temp_cur = 1 - cur;
 	return FX_OK;
 }
@@ -650,7 +665,8 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 
 // With obstacles set (a whole-grid context in fixed mode: fx_set_obstacles refuses the others) the solve is `iters` single-sweep launches of the
 // obstacle-aware kernel, the wide one where it applies; FX_FLAG_JACOBI_FUSE_MASK is ignored and the planner is not asked.  (Several
-// obstacle-aware sweeps per launch, in the manner of the strip and block families, do not exist yet.)
+// obstacle-aware sweeps per launch, in the manner of the strip and block families, do not exist yet.)  Open walls (fx_set_open_walls, on the
+// same terms) take the same route with the kernels of fx_open.hip, with or without a code volume.
 static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
 {
 	fx_ctx* ctx = lead;                                                 // FX_HIP reports through `ctx`
@@ -658,7 +674,8 @@ static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
 	ScopedMark mk(ctx, s, MK_JACOBI);
 	const Range r = owned(ctx);
 	for (uint32_t i = 0; i < iters; ++i) {
-		FX_HIP(launch_jacobi_obs(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], r.lo, r.hi, s));
+		if (ctx->open_faces) FX_HIP(launch_jacobi_open(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], ctx->open_faces, r.lo, r.hi, s));
+		else FX_HIP(launch_jacobi_obs(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], r.lo, r.hi, s));
 		ctx->p_cur ^= 1;
 		mk.launches += 1; mk.sweeps += 1;
 	}
@@ -667,7 +684,7 @@ static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
 
 int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters)
 {
-	if (lead->obst_code) return jacobi_obstacle(lead, s, iters);
+	if (lead->obst_code || lead->open_faces) return jacobi_obstacle(lead, s, iters);
 	if (overlap_level(lead) >= 2) {
 		std::vector<JacobiPolicy> pol{ policy_of(lead) };
 		for (fx_ctx* m : M) pol.push_back(policy_of(m));
@@ -689,6 +706,10 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	const Range r = owned(ctx);
 	int* rec = multi_rank(ctx) ? ctx->step_rec : nullptr;           // slab ranks: the projection also measures the next advection's need
 	ctx->rec_in_project = false;
+	if (ctx->open_faces) {
+		FX_HIP(launch_project_open(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], ctx->open_faces, r.lo, r.hi, s));
+		return FX_OK;
+	}
 	if (ctx->obst_code) {
 		FX_HIP(launch_project_obs(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], r.lo, r.hi, s));
 		return FX_OK;
@@ -714,6 +735,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		for (fx_ctx* m : M) m->col_halo_buf = (int)m->frame_parity;
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
+		for (fx_ctx* m : M) if ((rc = open_inflow_phase(m, CS(m, s)))) return rc;  // (whole-grid contexts with an open wall only)
 		for (fx_ctx* m : M) if ((rc = emit_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with emitters set only)
 		for (fx_ctx* m : M) if ((rc = heat_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with buoyancy on only)
 		for (fx_ctx* m : M) if ((rc = enforce_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with obstacles set only)

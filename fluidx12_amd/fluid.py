@@ -335,6 +335,25 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_enforce_obstacles(self._ctx, stream), "EnforceObstacles")
 
+    def SetOpenWalls(self, faces):
+        """the faces of the box through which the smoke leaves (fx_set_open_walls): a set of capi.WALL_* bits, 0 = all closed (default).  Beyond
+        an open face the pressure is 0, the smoke is clear air and the temperature ambient; the projection does not damp flow towards it.
+        Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid, fixed-mode contexts only; no z face on a 2-D grid."""
+        self._need()
+        capi.check(self._lib.fx_set_open_walls(self._ctx, int(faces)), "SetOpenWalls")
+
+    def GetOpenWalls(self):
+        """the setting in force (fx_get_open_walls)"""
+        self._need()
+        faces = C.c_uint32(0)
+        capi.check(self._lib.fx_get_open_walls(self._ctx, C.byref(faces)), "GetOpenWalls")
+        return int(faces.value)
+
+    def OpenInflow(self, stream=None):
+        """the inflow stage alone, in place on COLOR (fx_open_inflow): run it directly behind Advect; Advect does not include it"""
+        self._need()
+        capi.check(self._lib.fx_open_inflow(self._ctx, stream), "OpenInflow")
+
     def SetBuoyancy(self, ambient=0.0, density_weight=0.0, lift=0.0, cooling=0.0, up=(0.0, 1.0, 0.0), flags=0):
         """buoyancy (fx_set_buoyancy): a temperature field advected with the flow, cooling towards `ambient` by max(1 - cooling * dt, 0) per step,
         and the force (-density_weight * COLOR.w + lift * (T - ambient)) * up on VELOCITY1, one pass behind the emitters.  `up` is used as given.

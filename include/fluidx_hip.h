@@ -368,6 +368,53 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells);
 int fx_enforce_obstacles(fx_ctx* ctx, void* stream);
 
+/* Open walls (no reference counterpart: the reference's box is closed on all six faces -- the clamped neighbour indices of its stages and the
+ * wall damping of its projection).  fx_set_open_walls names the faces through which the smoke may leave; the step is then
+ *   advect -> inflow -> emit -> heat -> enforce -> confine -> divergence -> relaxation -> projection.
+ * "Beyond an open face" = a stencil neighbour whose UNCLAMPED index is -1 or N on an axis whose face there is open.  Rule by rule, every
+ * operation rounded as written, S = the obstacle mask (all 0 without one), n-a / n+a as in the obstacle block above:
+ *   divergence  unchanged (the plain or the obstacle one): the clamped neighbour is the zero-gradient velocity ghost already
+ *   relaxation  ((((((L - b) + R) + U) + D) + F) + B) * (1/6) (the constant 0x3e2aaaab; 2-D: four terms, * 0.25), each neighbour read as
+ *               beyond an open face ? +0 : S(n) ? p(c) : p(n)   -- a Dirichlet ghost p = 0; 0 in a solid cell
+ *   projection  grad_a = -q(n-) + q(n+) with the same q, u[a] = fma(-grad_a, k, u[a]); then the free-slip rule of the obstacles; then the wall
+ *               damping, which is skipped for axis a (factor 1) when pos < 0 and the low face of a is open or pos > 0 and the high face is
+ *               (pos = the cell centre in [-1, 1], as the plain projection forms it); 0 in all three components of a solid cell
+ *   inflow      a pass of its own directly behind the advection and in front of the emitters, dt > 0 only: the ghost cells beyond an open face
+ *               hold clear air.  Per axis with u0 = VELOCITY (the field the advection traced with), exactly as the buoyancy's step 1:
+ *                 p = (i + .5) / N      a = fma(-u0, dt, p)      t = a * N - 0.5      i0 = floor(t)      f = t - i0
+ *                 low face open:   w_a = 0 if i0 < -1,   f if i0 == -1,        else 1
+ *                 high face open:  w_a = 0 if i0 >= N,   1 - f if i0 == N - 1, else 1          (an axis with no open face: w_a = 1)
+ *                 w = (w_x * w_y) * w_z (2-D grids: w_x * w_y)      COLOR[c] = COLOR[c] * w, all four channels
+ *               an fp32 multiply; fp16 storage widens on load and rounds each channel once (RNE); a cell with w == 1 keeps its bits.
+ *               In real arithmetic this IS the advection's sample with zero ghost taps wherever both taps of an axis clamp onto the edge
+ *               cell (weights 1 - f and f on one value), and the same holds under mirror addressing (-1 -> 0, N -> N - 1).  The velocity
+ *               keeps its clamped (zero-gradient) sample.  The built-in impulse adds inside the advection, in front of this pass: what it
+ *               adds to a cell is scaled with the cell (an emitter's contribution, added behind the pass, is not).
+ *   temperature (fx_set_buoyancy) the ghost is at ambient: between its steps 1 and 2 the buoyancy pass forms Ts = fma(w, Ts - Ta, Ta) with w
+ *               from the i0 and f it already holds.  With all faces closed its arithmetic is unchanged.
+ * fx_set_open_walls: faces = a set of FX_WALL_* bits; 0 = all closed, the default: every call behaves exactly as without this function.
+ * FX_E_INVALID, the previous setting staying in force, for bits above 0x3F, a z bit on a 2-D grid, a context that owns fewer planes than
+ * the grid (slab ranks of every transport, on the obstacles' footing) and FX_JACOBI_FAITHFUL contexts (the freeze solve has no such
+ * kernels); FX_E_STATE for FX_FLAG_RENDER_ONLY (all three calls).  Obstacles, emitters, buoyancy, confinement, 2-D grids, both storages and
+ * both address modes are served together with open walls; without a mask the open kernels read no code byte.
+ * As with obstacles the pressure solve then runs one sweep per launch and ignores FX_FLAG_JACOBI_FUSE_MASK (jacobi_launches = jacobi_sweeps).
+ * Configuration like the confinement: per context, kept across fx_update_frame, not checkpointed (set it again after fx_checkpoint_load),
+ * not part of fx_field_digest.
+ * fx_open_inflow: the inflow stage alone, beside fx_emit / fx_heat (fx_advect does not include it), with the time step of the last
+ * fx_update_frame; nothing (FX_OK) with all faces closed or dt <= 0.  fx_jacobi / fx_project / fx_heat follow the setting.
+ * Timing: the inflow pass is booked into fx_timing.advect_ms.
+ * Out of scope: open walls on slab ranks; open walls in faithful mode; several open-wall sweeps per launch; velocity ghosts other than
+ * zero-gradient; checkpointing the setting. */
+#define FX_WALL_X_LO 0x01u   /* the code byte's order: x-, x+, y-, y+, z-, z+ */
+#define FX_WALL_X_HI 0x02u
+#define FX_WALL_Y_LO 0x04u
+#define FX_WALL_Y_HI 0x08u   /* "up" for the built-in impulse and fx_buoyancy's default */
+#define FX_WALL_Z_LO 0x10u
+#define FX_WALL_Z_HI 0x20u
+int fx_set_open_walls(fx_ctx* ctx, uint32_t faces);
+int fx_get_open_walls(fx_ctx* ctx, uint32_t* faces);
+int fx_open_inflow(fx_ctx* ctx, void* stream);
+
 /* Buoyancy (Fedkiw, Stam, Jensen 2001, eq. 8; no reference counterpart -- the reference's only lift is the constant force inside its impulse
  * ball): a temperature T that is advected with the flow, cools towards an ambient value and, with the smoke density rho = COLOR.w, pushes
  * the velocity along `up`:   f = (-density_weight * rho + lift * (T - ambient)) * up.   With buoyancy on, fx_simulate runs one more pass
