@@ -94,8 +94,8 @@ int heat_plan(const Geom& g, const fx_buoyancy& b, const fx_heat_source* list, i
 // faces: the open walls (FX_WALL_* bits, 0 = none): the sample is blended towards the ambient value by open_wall_weight of each axis
 hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
 	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s, unsigned faces = 0);
-// ---- open walls (fx_open.hip), whole grids only (hipErrorNotSupported for a slab geometry).  faces: FX_WALL_* bits, the code byte's bit order
-// (x-, x+, y-, y+, z-, z+; no z bit on a 2-D grid: hipErrorInvalidValue); code: the obstacle bytes or null (then no code byte is read)
+// ---- open walls (the inflow pass: fx_open.hip; the sweeps and the projection: the bnd launchers below), whole grids only (hipErrorNotSupported
+// for a slab geometry).  faces: FX_WALL_* bits, the code byte's bit order (x-, x+, y-, y+, z-, z+; no z bit on a 2-D grid: hipErrorInvalidValue)
 // The share of a linear sample at t = i0 + f (i0 = fl = floor(t), taps i0 and i0 + 1 of an axis of n cells) that lies inside the box when the
 // cells beyond an open face are empty: low face open: 0 for i0 < -1, f for i0 == -1; high face open: 0 for i0 >= n, 1 - f for i0 == n - 1; else 1
 __host__ __device__ inline float open_wall_weight(float fl, float f, int n, unsigned lo_open, unsigned hi_open)
@@ -115,11 +115,6 @@ __host__ __device__ inline float open_wall_trace(float u0, float dt, int i, int 
 	return open_wall_weight(fl, t - fl, n, lo_open, hi_open);
 }
 const int kOpenTileX = 64, kOpenTileY = 4;
-bool jacobi_open_takes_v4(const Geom& g);    // 3-D, X % 4 == 0: four cells per thread; else the scalar kernel
-hipError_t launch_jacobi_open(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, unsigned faces,
-	int z_begin, int z_end, hipStream_t s);   // one sweep
-hipError_t launch_project_open(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
-	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
 // the inflow pass, in place on a whole-grid colour: COLOR *= w of the back-trace with vel0; alpha: the render's side volume when it holds this
 // colour field's alpha, else null
 hipError_t launch_open_inflow(const Geom& g, int half_store, const void* vel0, void* col, float* alpha, unsigned faces, float dt, hipStream_t s);
@@ -135,10 +130,13 @@ long long obstacle_enforce_tiles(const int lo[3], const int hi[3], int* x0, int*
 hipError_t launch_obstacle_enforce(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3], void* vel, void* col,
 	float* alpha, hipStream_t s);
 hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel, const uint8_t* code, float* b, int z_begin, int z_end, hipStream_t s);
-bool jacobi_obs_takes_v4(const Geom& g);     // 3-D, X % 4 == 0: four cells per thread; else the scalar kernel
-hipError_t launch_jacobi_obs(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, int z_begin, int z_end, hipStream_t s);   // one sweep
-hipError_t launch_project_obs(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
-	void* vel_out, int z_begin, int z_end, hipStream_t s);
+// the boundary-aware sweep (one per launch; 3-D, X % 4 == 0: four cells per thread, else the scalar kernel) and projection, for obstacles,
+// open walls or both.  code: the obstacle bytes, or null (then no code byte is read); faces: the open walls' FX_WALL_* bits, or 0 (all closed);
+// neither: hipErrorInvalidValue, that is the plain kernels' case
+hipError_t launch_jacobi_bnd(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, unsigned faces,
+	int z_begin, int z_end, hipStream_t s);
+hipError_t launch_project_bnd(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

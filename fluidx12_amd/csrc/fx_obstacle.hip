@@ -1,19 +1,29 @@
-// fx_obstacle.hip -- voxelised solid obstacles inside the box (fx_set_obstacles), gfx950.  No reference counterpart: the reference's only
-// boundaries are the six walls (the clamped neighbour indices of its projection shaders); Harris / Crane et al. (GPU Gems 3, ch. 30) is the scheme.
+// fx_obstacle.hip -- the boundary-aware pressure kernels, gfx950: voxelised solid obstacles inside the box (fx_set_obstacles) and open walls
+// (fx_set_open_walls; their inflow pass is fx_open.hip).  No reference counterpart: the reference's only boundaries are six closed walls (the
+// clamped neighbour indices of its projection shaders); Harris / Crane et al. (GPU Gems 3, ch. 30) is the scheme of the solids.
 //
 //   k_obstacle_codes    mask uint8[Z][Y][X] -> one code byte per cell (+ the count of solid cells and their bounding box)
 //   k_obstacle_enforce  solid cells: VELOCITY1, COLOR (and the render's alpha side volume) become +0; over the solids' bounding box only
 //   k_divergence_obs    k_divergence with  v(n) -> S(n) ? 0 : v(n),  b = 0 in a solid cell
-//   k_jacobi_obs(_v4)   one lock-step sweep with  p(n) -> S(n) ? p(c) : p(n),  p_out = 0 in a solid cell
-//   k_project_obs       k_project with the same pressure substitution, u[a] = 0 beside a solid along a (free slip), 0 in a solid cell
+//   k_jacobi_bnd(_v4)   one lock-step sweep with  p(n) -> q(n) = beyond an open face ? +0 : S(n) ? p(c) : p(n),  p_out = 0 in a solid cell
+//   k_project_bnd       k_project with the same q, u[a] = 0 beside a solid along a (free slip), 0 in a solid cell, and no wall damping of
+//                       axis a towards an open face of a
 //
 // The wall rule of the plain kernels is "a neighbour that is not there reads as the cell itself" (clamped indices); a solid extends it to
 // neighbours inside an obstacle.  The stencil kernels never read the mask: the code byte of a cell holds S of its six CLAMPED neighbours
 // (bit 0..5: x-1, x+1, y-1, y+1, z-1, z+1; the z bits are 0 on 2-D grids) and of the cell itself (bit 6), built once per fx_set_obstacles.
-// Every substitution is a select on a loaded value -- no branch, no divergence -- and with an all-zero mask each kernel is, operation for
-// operation, its plain counterpart of fx_sim.hip (tests/test_gpu_obstacles.py holds them bit for bit against each other and against
-// tests/obstacle_ref/).  fp32 arithmetic in the plain kernels' association order; fp16 storage widens on load and rounds once (RNE) on store.
-// Whole grids only (fx_set_obstacles refuses slab ranks): local plane = global plane.
+// "Beyond an open face" = a stencil neighbour whose unclamped index is -1 or N on an axis whose face there is open (FX_WALL_*: the code
+// byte's bit order), a Dirichlet ghost p = 0.  The divergence has no open rule: its clamped neighbour is the zero-gradient velocity ghost
+// already.  The open rule costs no bytes: it replaces the clamped replica of a cell by +0 at the ends of a row and in the rows / planes on a
+// face, which are then not loaded at all.
+// The bnd kernels are templated on CODE (a code volume is present) and OPEN (a face is open), and three combinations exist: (1, 0) obstacles
+// in a closed box, (1, 1) both, (0, 1) open walls alone, which read no code byte (12 bytes per cell and sweep; 13 with).  Without either the
+// plain kernels of fx_sim.hip run.  With OPEN = 0 the faces are a compile-time zero and nothing of the open rule is left in the kernel.
+// Every substitution is a select on a loaded value -- no branch, no divergence -- and with an all-zero mask and no open face each kernel is,
+// operation for operation, its plain counterpart of fx_sim.hip (tests/test_gpu_obstacles.py holds them bit for bit against each other and
+// against tests/obstacle_ref/, tests/test_gpu_open_walls.py against the numpy model tests/open_ref.py).  fp32 arithmetic in the plain
+// kernels' association order; fp16 storage widens on load and rounds once (RNE) on store.
+// Whole grids only (fx_set_obstacles and fx_set_open_walls refuse slab ranks): local plane = global plane.
 #include "fx_internal.h"
 
 namespace fx {
@@ -60,6 +70,20 @@ __device__ __forceinline__ Tile3 tile_of(int gx, int gy, int gz, int remap)
 	o.y = u % gy;
 	o.z = u / gy;
 	return o;
+}
+
+// the faces a cell's neighbours lie beyond: bit a of `faces` survives where the cell sits on that face (the z bits never on a 2-D grid:
+// fx_set_open_walls refuses them)
+__device__ __forceinline__ unsigned beyond_of(const Geom& g, unsigned faces, int x, int y, int z)
+{
+	unsigned on = 0;
+	if (x == 0) on |= OB_XM;
+	if (x == g.X - 1) on |= OB_XP;
+	if (y == 0) on |= OB_YM;
+	if (y == g.Y - 1) on |= OB_YP;
+	if (z == 0) on |= OB_ZM;
+	if (z == g.Zg - 1) on |= OB_ZP;
+	return faces & on;
 }
 
 }  // namespace
@@ -172,11 +196,13 @@ __global__ __launch_bounds__(256) void k_divergence_obs(const Geom g, const type
 
 // ---------------------------------------------------------------------------------------------
 // Jacobi sweep, scalar: any extent, 2-D / 3-D
-//   x = ((((((qL - b) + qR) + qU) + qD) + qF) + qB) * (1/6)     2-D: ((((qL - b) + qR) + qU) + qD) * 1/4,   q(n) = S(n) ? p(c) : p(n)
+//   x = ((((((qL - b) + qR) + qU) + qD) + qF) + qB) * (1/6)     2-D: ((((qL - b) + qR) + qU) + qD) * 1/4
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_jacobi_obs(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
-	const uint8_t* __restrict__ code, float* __restrict__ p_out, int z_begin, int nzp, int remap)
+template <bool CODE, bool OPEN>
+__global__ __launch_bounds__(256) void k_jacobi_bnd(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
+	const uint8_t* __restrict__ code, float* __restrict__ p_out, unsigned faces_arg, int z_begin, int nzp, int remap)
 {
+	const unsigned faces = OPEN ? faces_arg : 0u;
 	const Tile3 tile = tile_of((g.X + 63) >> 6, (g.Y + 3) >> 2, nzp, remap);
 	const int x = tile.x * 64 + threadIdx.x;
 	const int y = tile.y * 4 + threadIdx.y;
@@ -185,22 +211,23 @@ __global__ __launch_bounds__(256) void k_jacobi_obs(const Geom g, const float* _
 	const size_t plane = g.plane();
 	const size_t zrow = (size_t)g.lz(z) * plane;
 	const size_t id = zrow + (size_t)y * g.X + x;
-	const unsigned k = code[id];
+	const unsigned k = CODE ? (unsigned)code[id] : 0u;
+	const unsigned o = beyond_of(g, faces, x, y, z);
 	const float c = p_in[id];
 	const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
 	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
 	const float L = p_in[zrow + (size_t)y * g.X + xl], R = p_in[zrow + (size_t)y * g.X + xr];
 	const float U = p_in[zrow + (size_t)yu * g.X + x], D = p_in[zrow + (size_t)yd * g.X + x];
-	float s = ((k & OB_XM) ? c : L) - b[id];
-	s = ((k & OB_XP) ? c : R) + s;
-	s = ((k & OB_YM) ? c : U) + s;
-	s = ((k & OB_YP) ? c : D) + s;
+	float s = ((o & OB_XM) ? 0.0f : (k & OB_XM) ? c : L) - b[id];
+	s = ((o & OB_XP) ? 0.0f : (k & OB_XP) ? c : R) + s;
+	s = ((o & OB_YM) ? 0.0f : (k & OB_YM) ? c : U) + s;
+	s = ((o & OB_YP) ? 0.0f : (k & OB_YP) ? c : D) + s;
 	float inv = 0.25f;
 	if (g.Zg > 1) {
 		const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
 		const float F = p_in[(size_t)g.lz(zf) * plane + (size_t)y * g.X + x], B = p_in[(size_t)g.lz(zb) * plane + (size_t)y * g.X + x];
-		s = ((k & OB_ZM) ? c : F) + s;
-		s = ((k & OB_ZP) ? c : B) + s;
+		s = ((o & OB_ZM) ? 0.0f : (k & OB_ZM) ? c : F) + s;
+		s = ((o & OB_ZP) ? 0.0f : (k & OB_ZP) ? c : B) + s;
 		inv = __uint_as_float(0x3e2aaaabu);
 	}
 	p_out[id] = (k & OB_SELF) ? 0.0f : s * inv;
@@ -208,12 +235,17 @@ __global__ __launch_bounds__(256) void k_jacobi_obs(const Geom g, const float* _
 
 // ---------------------------------------------------------------------------------------------
 // Jacobi sweep, 3-D, X % 4 == 0: k_jacobi_v4's scheme (one thread = 4 consecutive x: 16-byte loads of the five p rows and of b, a 16-byte
-// store, the x neighbours of the row's ends through DPP lane shifts) + ONE 4-byte load for the four cells' codes: 13 bytes per cell and
-// sweep against 12.  Twenty-four selects and four for the solid cells themselves; bit-identical to k_jacobi_obs.
+// store, the x neighbours of the row's ends through DPP lane shifts) + with CODE one 4-byte load for the four cells' codes: 13 bytes per
+// cell and sweep against 12, twenty-four selects and four for the solid cells themselves.  With OPEN the clamped replica becomes +0 at
+// x4 == 0 / X4 - 1 and in the rows and planes on an open face, whose row beyond is not loaded.  A cell on a face is its own clamped
+// neighbour there, so its code bit for that side is its own solid bit: the select behind the +0 only ever changes a solid cell, whose
+// result is 0 whatever it summed.  Bit-identical to k_jacobi_bnd.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_jacobi_obs_v4(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
-	const uint8_t* __restrict__ code, float* __restrict__ p_out, int z_begin, int nzp, int remap, int rows_per_block)
+template <bool CODE, bool OPEN>
+__global__ __launch_bounds__(256) void k_jacobi_bnd_v4(const Geom g, const float* __restrict__ p_in, const float* __restrict__ b,
+	const uint8_t* __restrict__ code, float* __restrict__ p_out, unsigned faces_arg, int z_begin, int nzp, int remap, int rows_per_block)
 {
+	const unsigned faces = OPEN ? faces_arg : 0u;
 	const int X4 = g.X >> 2;
 	const int lane = threadIdx.x;                       // float4 column
 	const Tile3 tile = tile_of((X4 + (int)blockDim.x - 1) / (int)blockDim.x, (g.Y + rows_per_block - 1) / rows_per_block, nzp, remap);
@@ -226,20 +258,25 @@ __global__ __launch_bounds__(256) void k_jacobi_obs_v4(const Geom g, const float
 	const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
 	const size_t zrow = (size_t)g.lz(z) * plane;
 	const size_t c_off = zrow + (size_t)y * g.X + 4 * x4;
+	const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	const bool oU = (faces & OB_YM) && y == 0, oD = (faces & OB_YP) && y == g.Y - 1;
+	const bool oF = (faces & OB_ZM) && z == 0, oB = (faces & OB_ZP) && z == g.Zg - 1;
 	const float4 c = *reinterpret_cast<const float4*>(p_in + c_off);
-	const float4 U = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yu * g.X + 4 * x4);
-	const float4 D = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yd * g.X + 4 * x4);
-	const float4 F = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zf) * plane + (size_t)y * g.X + 4 * x4);
-	const float4 B = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zb) * plane + (size_t)y * g.X + 4 * x4);
+	float4 U = zero4, D = zero4, F = zero4, B = zero4;                         // (a row or plane beyond an open face is not loaded)
+	if (!oU) U = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yu * g.X + 4 * x4);
+	if (!oD) D = *reinterpret_cast<const float4*>(p_in + zrow + (size_t)yd * g.X + 4 * x4);
+	if (!oF) F = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zf) * plane + (size_t)y * g.X + 4 * x4);
+	if (!oB) B = *reinterpret_cast<const float4*>(p_in + (size_t)g.lz(zb) * plane + (size_t)y * g.X + 4 * x4);
 	const float4 bb = *reinterpret_cast<const float4*>(b + c_off);
-	const uint32_t kk = *reinterpret_cast<const uint32_t*>(code + c_off);      // (X % 4 == 0: every group of four cells is 4-byte aligned)
+	uint32_t kk = 0;
+	if (CODE) kk = *reinterpret_cast<const uint32_t*>(code + c_off);           // (X % 4 == 0: every group of four cells is 4-byte aligned)
 	// x neighbours: the adjacent float4 column sits in the adjacent lane (DPP wave_shr:1 / wave_shl:1, as k_jacobi_v4); only a wave's
 	// first / last lane inside a row still loads them
 	const int wl = (int)((threadIdx.y * blockDim.x + threadIdx.x) & 63);
 	float L = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, c.w), 0x138, 0xf, 0xf, false));
 	float R = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, c.x), 0x130, 0xf, 0xf, false));
-	if (x4 == 0) L = c.x; else if (wl == 0 || lane == 0) L = p_in[c_off - 1];
-	if (x4 == X4 - 1) R = c.w; else if (wl == 63 || lane == (int)blockDim.x - 1) R = p_in[c_off + 4];
+	if (x4 == 0) L = (faces & OB_XM) ? 0.0f : c.x; else if (wl == 0 || lane == 0) L = p_in[c_off - 1];
+	if (x4 == X4 - 1) R = (faces & OB_XP) ? 0.0f : c.w; else if (wl == 63 || lane == (int)blockDim.x - 1) R = p_in[c_off + 4];
 	const float inv = __uint_as_float(0x3e2aaaabu);
 	const float pc[4] = { c.x, c.y, c.z, c.w };
 	const float pl[4] = { L, c.x, c.y, c.z }, pr[4] = { c.y, c.z, c.w, R };
@@ -249,26 +286,37 @@ __global__ __launch_bounds__(256) void k_jacobi_obs_v4(const Geom g, const float
 	float o[4];
 #pragma unroll
 	for (int i = 0; i < 4; ++i) {
-		const unsigned k = kk >> (8 * i);
-		float s = ((k & OB_XM) ? pc[i] : pl[i]) - bv[i];
-		s = ((k & OB_XP) ? pc[i] : pr[i]) + s;
-		s = ((k & OB_YM) ? pc[i] : pu[i]) + s;
-		s = ((k & OB_YP) ? pc[i] : pd[i]) + s;
-		s = ((k & OB_ZM) ? pc[i] : pf[i]) + s;
-		s = ((k & OB_ZP) ? pc[i] : pb[i]) + s;
-		o[i] = (k & OB_SELF) ? 0.0f : s * inv;
+		if (CODE) {
+			const unsigned k = kk >> (8 * i);
+			float s = ((k & OB_XM) ? pc[i] : pl[i]) - bv[i];
+			s = ((k & OB_XP) ? pc[i] : pr[i]) + s;
+			s = ((k & OB_YM) ? pc[i] : pu[i]) + s;
+			s = ((k & OB_YP) ? pc[i] : pd[i]) + s;
+			s = ((k & OB_ZM) ? pc[i] : pf[i]) + s;
+			s = ((k & OB_ZP) ? pc[i] : pb[i]) + s;
+			o[i] = (k & OB_SELF) ? 0.0f : s * inv;
+		} else {
+			float s = pl[i] - bv[i];
+			s = pr[i] + s;
+			s = pu[i] + s;
+			s = pd[i] + s;
+			s = pf[i] + s;
+			s = pb[i] + s;
+			o[i] = s * inv;
+		}
 	}
 	*reinterpret_cast<float4*>(p_out + c_off) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
 // ---------------------------------------------------------------------------------------------
-// projection + free slip against the solids + wall damping
+// projection + free slip against the solids + wall damping, none of it towards an open face
 // ---------------------------------------------------------------------------------------------
-template <bool HALF>
-__global__ __launch_bounds__(256) void k_project_obs(const Geom g, const SimParams sp,
+template <bool HALF, bool CODE, bool OPEN>
+__global__ __launch_bounds__(256) void k_project_bnd(const Geom g, const SimParams sp,
 	const typename Sto<HALF>::S* __restrict__ vel_in, const float* __restrict__ p, const uint8_t* __restrict__ code,
-	typename Sto<HALF>::S* __restrict__ vel_out, int z_begin, int nzp, int remap)
+	typename Sto<HALF>::S* __restrict__ vel_out, unsigned faces_arg, int z_begin, int nzp, int remap)
 {
+	const unsigned faces = OPEN ? faces_arg : 0u;
 	typedef Sto<HALF> St;
 	const Tile3 tile = tile_of((g.X + 63) >> 6, (g.Y + 3) >> 2, nzp, remap);
 	const int x = tile.x * 64 + threadIdx.x;
@@ -278,7 +326,8 @@ __global__ __launch_bounds__(256) void k_project_obs(const Geom g, const SimPara
 	const size_t plane = g.plane(), stride = g.cells_local();
 	const size_t zrow = (size_t)g.lz(z) * plane;
 	const size_t id = zrow + (size_t)y * g.X + x;
-	const unsigned k = code[id];
+	const unsigned k = CODE ? (unsigned)code[id] : 0u;
+	const unsigned o = beyond_of(g, faces, x, y, z);
 	const int xl = max(x, 1) - 1, xr = min(x + 1, g.X - 1);
 	const int yu = max(y, 1) - 1, yd = min(y + 1, g.Y - 1);
 	float u[3] = { St::ld(vel_in, id), St::ld(vel_in, stride + id), St::ld(vel_in, 2 * stride + id) };
@@ -286,14 +335,14 @@ __global__ __launch_bounds__(256) void k_project_obs(const Geom g, const SimPara
 	const float L = p[zrow + (size_t)y * g.X + xl], R = p[zrow + (size_t)y * g.X + xr];
 	const float U = p[zrow + (size_t)yu * g.X + x], D = p[zrow + (size_t)yd * g.X + x];
 	float grad[3];
-	grad[0] = -((k & OB_XM) ? c : L) + ((k & OB_XP) ? c : R);
-	grad[1] = -((k & OB_YM) ? c : U) + ((k & OB_YP) ? c : D);
+	grad[0] = -((o & OB_XM) ? 0.0f : (k & OB_XM) ? c : L) + ((o & OB_XP) ? 0.0f : (k & OB_XP) ? c : R);
+	grad[1] = -((o & OB_YM) ? 0.0f : (k & OB_YM) ? c : U) + ((o & OB_YP) ? 0.0f : (k & OB_YP) ? c : D);
 	grad[2] = 0.0f;
 	float kd = 0.5f;
 	if (sp.is3d) {
 		const int zf = max(z, 1) - 1, zb = min(z + 1, g.Zg - 1);
 		const float F = p[(size_t)g.lz(zf) * plane + (size_t)y * g.X + x], B = p[(size_t)g.lz(zb) * plane + (size_t)y * g.X + x];
-		grad[2] = -((k & OB_ZM) ? c : F) + ((k & OB_ZP) ? c : B);
+		grad[2] = -((o & OB_ZM) ? 0.0f : (k & OB_ZM) ? c : F) + ((o & OB_ZP) ? 0.0f : (k & OB_ZP) ? c : B);
 		kd = __uint_as_float(0x3f855556u);                                 // 0.5f / 0.48f, as k_project
 		u[2] = fmaf(-grad[2], kd, u[2]);
 	}
@@ -306,12 +355,13 @@ __global__ __launch_bounds__(256) void k_project_obs(const Geom g, const SimPara
 	const int cell[3] = { x, y, z };
 	const float dims[3] = { (float)g.X, (float)g.Y, (float)g.Zg };
 #pragma unroll
-	for (int a = 0; a < 3; ++a) {                                          // the wall damping of k_project
+	for (int a = 0; a < 3; ++a) {                                          // the wall damping of k_project, except towards an open face
 		float pos = ((float)cell[a] + 0.5f) / dims[a];
 		if (sp.is3d || a < 2) pos = fmaf(pos, 2.0f, -1.0f);
 		float f = (-fabsf(pos) + 0.970000029f) * 33.3333359f;
 		f = fminf(fmaxf(f, -1.0f), 1.0f);
-		const float w = (0.0f < u[a] * pos) ? f : 1.0f;
+		const bool open = (pos < 0.0f && ((faces >> (2 * a)) & 1u)) || (pos > 0.0f && ((faces >> (2 * a + 1)) & 1u));
+		const float w = (0.0f < u[a] * pos && !open) ? f : 1.0f;
 		St::st(vel_out, a * stride + id, (k & OB_SELF) ? 0.0f : u[a] * w);
 	}
 }
@@ -376,35 +426,56 @@ hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel,
 	return hipGetLastError();
 }
 
-// OBSTACLE_V4 = 0 (lab builds): the scalar kernel on every geometry -- what tests/test_gpu_obstacles.py holds the wide one against
-bool jacobi_obs_takes_v4(const Geom& g) { return g.Zg > 1 && (g.X & 3) == 0 && FX_KNOB_INT("OBSTACLE_V4", 1) != 0; }
-
-hipError_t launch_jacobi_obs(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, int z_begin, int z_end, hipStream_t s)
+// ---- the bnd family.  code may be null (open walls alone), faces may be 0 (obstacles in a closed box); not both: those are the plain kernels
+static inline bool faces_ok(const Geom& g, unsigned faces) { return !(faces & ~0x3Fu) && !(g.Zg <= 1 && (faces & (OB_ZM | OB_ZP))); }
+static inline hipError_t bnd_args(const Geom& g, const uint8_t* code, unsigned faces, int z_begin, int z_end)
 {
 	if (!whole_grid(g)) return hipErrorNotSupported;
+	return faces_ok(g, faces) && (code || faces) && z_begin >= 0 && z_end <= g.Zg ? hipSuccess : hipErrorInvalidValue;
+}
+// the wide sweep.  OBSTACLE_V4 = 0 (lab builds): the scalar kernel on every geometry -- what tests/test_gpu_obstacles.py and
+// tests/test_gpu_open_walls.py hold the wide one against
+static bool jacobi_bnd_takes_v4(const Geom& g) { return g.Zg > 1 && (g.X & 3) == 0 && FX_KNOB_INT("OBSTACLE_V4", 1) != 0; }
+
+hipError_t launch_jacobi_bnd(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, unsigned faces,
+	int z_begin, int z_end, hipStream_t s)
+{
+	const hipError_t e = bnd_args(g, code, faces, z_begin, z_end);
+	if (e != hipSuccess) return e;
 	const int nzp = z_end - z_begin;
 	if (nzp <= 0) return hipSuccess;
-	if (jacobi_obs_takes_v4(g)) {
+	if (jacobi_bnd_takes_v4(g)) {
 		const int X4 = g.X >> 2;                         // the block shape of k_jacobi_v4's launch
 		const int bx = X4 < 64 ? X4 : 64;
 		int by = 256 / bx; if (by < 1) by = 1; if (by > g.Y) by = g.Y;
 		const dim3 block(bx, by, 1), grid(((X4 + bx - 1) / bx) * ((g.Y + by - 1) / by) * nzp, 1, 1);
-		hipLaunchKernelGGL(k_jacobi_obs_v4, grid, block, 0, s, g, p_in, b, code, p_out, z_begin, nzp, 1, by);
+		const auto k = !faces ? k_jacobi_bnd_v4<true, false> : code ? k_jacobi_bnd_v4<true, true> : k_jacobi_bnd_v4<false, true>;
+		hipLaunchKernelGGL(k, grid, block, 0, s, g, p_in, b, code, p_out, faces, z_begin, nzp, 1, by);
 	} else {
-		hipLaunchKernelGGL(k_jacobi_obs, grid_cells(g, nzp), dim3(64, 4, 1), 0, s, g, p_in, b, code, p_out, z_begin, nzp, 1);
+		const auto k = !faces ? k_jacobi_bnd<true, false> : code ? k_jacobi_bnd<true, true> : k_jacobi_bnd<false, true>;
+		hipLaunchKernelGGL(k, grid_cells(g, nzp), dim3(64, 4, 1), 0, s, g, p_in, b, code, p_out, faces, z_begin, nzp, 1);
 	}
 	return hipGetLastError();
 }
 
-hipError_t launch_project_obs(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
-	void* vel_out, int z_begin, int z_end, hipStream_t s)
+template <bool HALF>
+static hipError_t launch_project_bnd_t(const Geom& g, const SimParams& sp, const void* vel_in, const float* p, const uint8_t* code, void* vel_out,
+	unsigned faces, int z_begin, int nzp, hipStream_t s)
 {
-	if (!whole_grid(g)) return hipErrorNotSupported;
-	if (z_end <= z_begin) return hipSuccess;
-	const dim3 grid = grid_cells(g, z_end - z_begin), block(64, 4, 1);
-	if (half_store) hipLaunchKernelGGL(k_project_obs<true>, grid, block, 0, s, g, sp, (const h16*)vel_in, p, code, (h16*)vel_out, z_begin, z_end - z_begin, remap_small(g));
-	else hipLaunchKernelGGL(k_project_obs<false>, grid, block, 0, s, g, sp, (const float*)vel_in, p, code, (float*)vel_out, z_begin, z_end - z_begin, remap_small(g));
+	typedef typename Sto<HALF>::S S;
+	const auto k = !faces ? k_project_bnd<HALF, true, false> : code ? k_project_bnd<HALF, true, true> : k_project_bnd<HALF, false, true>;
+	hipLaunchKernelGGL(k, grid_cells(g, nzp), dim3(64, 4, 1), 0, s, g, sp, (const S*)vel_in, p, code, (S*)vel_out, faces, z_begin, nzp, remap_small(g));
 	return hipGetLastError();
+}
+
+hipError_t launch_project_bnd(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s)
+{
+	const hipError_t e = bnd_args(g, code, faces, z_begin, z_end);
+	if (e != hipSuccess) return e;
+	if (z_end <= z_begin) return hipSuccess;
+	return half_store ? launch_project_bnd_t<true>(g, sp, vel_in, p, code, vel_out, faces, z_begin, z_end - z_begin, s)
+	                  : launch_project_bnd_t<false>(g, sp, vel_in, p, code, vel_out, faces, z_begin, z_end - z_begin, s);
 }
 
 }  // namespace fx

@@ -663,10 +663,9 @@ static int jacobi_overlapped(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t 
 #undef FX_FIN
 }
 
-// With obstacles set (a whole-grid context in fixed mode: fx_set_obstacles refuses the others) the solve is `iters` single-sweep launches of the
-// obstacle-aware kernel, the wide one where it applies; FX_FLAG_JACOBI_FUSE_MASK is ignored and the planner is not asked.  (Several
-// obstacle-aware sweeps per launch, in the manner of the strip and block families, do not exist yet.)  Open walls (fx_set_open_walls, on the
-// same terms) take the same route with the kernels of fx_open.hip, with or without a code volume.
+// With obstacles set or a wall open (a whole-grid context in fixed mode: fx_set_obstacles and fx_set_open_walls refuse the others) the solve is
+// `iters` single-sweep launches of the boundary-aware kernel (fx_obstacle.hip), the wide one where it applies; FX_FLAG_JACOBI_FUSE_MASK is
+// ignored and the planner is not asked.  (Several such sweeps per launch, in the manner of the strip and block families, do not exist yet.)
 static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
 {
 	fx_ctx* ctx = lead;                                                 // FX_HIP reports through `ctx`
@@ -674,8 +673,7 @@ static int jacobi_obstacle(fx_ctx* lead, hipStream_t s, uint32_t iters)
 	ScopedMark mk(ctx, s, MK_JACOBI);
 	const Range r = owned(ctx);
 	for (uint32_t i = 0; i < iters; ++i) {
-		if (ctx->open_faces) FX_HIP(launch_jacobi_open(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], ctx->open_faces, r.lo, r.hi, s));
-		else FX_HIP(launch_jacobi_obs(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], r.lo, r.hi, s));
+		FX_HIP(launch_jacobi_bnd(ctx->g, ctx->p[ctx->p_cur], ctx->b, ctx->obst_code, ctx->p[ctx->p_cur ^ 1], ctx->open_faces, r.lo, r.hi, s));
 		ctx->p_cur ^= 1;
 		mk.launches += 1; mk.sweeps += 1;
 	}
@@ -706,12 +704,8 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	const Range r = owned(ctx);
 	int* rec = multi_rank(ctx) ? ctx->step_rec : nullptr;           // slab ranks: the projection also measures the next advection's need
 	ctx->rec_in_project = false;
-	if (ctx->open_faces) {
-		FX_HIP(launch_project_open(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], ctx->open_faces, r.lo, r.hi, s));
-		return FX_OK;
-	}
-	if (ctx->obst_code) {
-		FX_HIP(launch_project_obs(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], r.lo, r.hi, s));
+	if (ctx->obst_code || ctx->open_faces) {                        // obstacles, open walls or both: the boundary-aware projection
+		FX_HIP(launch_project_bnd(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], ctx->open_faces, r.lo, r.hi, s));
 		return FX_OK;
 	}
 	FX_HIP(launch_project(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->vel[0], r.lo, r.hi, s,

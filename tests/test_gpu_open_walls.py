@@ -117,6 +117,31 @@ def test_stages_match_the_model_bit_for_bit(dims, storage):
     f.Release()
 
 
+@pytest.mark.parametrize("dims", V4)
+def test_the_wide_sweep_is_the_scalar_sweep(dims, knob):
+    """every legal face open, with and without a mask: seven sweeps as built (the wide kernel), then on the lab build with the scalar one"""
+    faces = orf.legal_faces(dims)
+    masks = [None, random_mask(dims, seed=17)]
+    _, _, p = rand_state(dims, 311)
+    b = np.random.default_rng(313).standard_normal(p.shape).astype(f32)
+
+    def sweeps(m):
+        f = make(dims, jacobi_iters=7)
+        f.SetObstacles(m)
+        f.SetOpenWalls(faces)
+        f.upload(fx.FIELD_PRESSURE, p); f.upload(fx.FIELD_DIVERGENCE, b)
+        f.Jacobi(7)
+        out = f.download(fx.FIELD_PRESSURE)
+        f.Release()
+        return out
+    wide = [sweeps(m) for m in masks]
+    knob("OBSTACLE_V4", "0")                                          # (a lab switch: the contexts from here on run on the lab build)
+    scalar = [sweeps(m) for m in masks]
+    for m, w, s in zip(masks, wide, scalar):
+        want = orf.ref_jacobi(p, b, m, faces, 7)
+        assert same_bits(w, want) and same_bits(s, want), m is not None
+
+
 # ---- 2: the inflow pass ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("address", ["clamp", "mirror"])
 @pytest.mark.parametrize("storage", ["fp32", "fp16"])

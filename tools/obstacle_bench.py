@@ -5,7 +5,7 @@
 One process, four contexts on one grid (fp32 storage, fixed sweep count), stepped in turn so that every leg sees the same device state; the
 times are the device events of fx_timing.  Legs:
   A  no mask, FX_FLAG_JACOBI_FUSE = 1: one k_jacobi_v4 sweep per launch -- the yardstick of the obstacle sweep (12 bytes per cell and sweep)
-  B  an all-fluid mask: k_jacobi_obs_v4 (13 bytes per cell and sweep), k_divergence_obs, k_project_obs
+  B  an all-fluid mask: k_jacobi_bnd_v4<CODE = 1, OPEN = 0> (13 bytes per cell and sweep), k_divergence_obs, k_project_bnd<HALF, 1, 0>
   C  a ball of radius 0.15 at (0.5, 0.45, 0.5): the same kernels, and the enforce launch over the ball's bounding box
   D  no mask, default plan: what a context without obstacles runs (several sweeps per launch)
 Every repeat prints one line per leg: us per sweep, and divergence / projection / advection (with the enforce pass) / step in ms.

@@ -1,13 +1,13 @@
-"""What open walls cost (fx_set_open_walls, csrc/fx_open.hip): a table for docs/LAB.md, not a figure of bench.py.
+"""What open walls cost (fx_set_open_walls; csrc/fx_open.hip, the sweeps and the projection: csrc/fx_obstacle.hip): a table for docs/LAB.md, not a figure of bench.py.
 
     python tools/open_walls_bench.py [--grid 256] [--iters 40] [--steps 30] [--warmup 10] [--repeats 3] [--storage fp32] [--stage-reps 200] [--json out.json]
 
 One process, four contexts on one grid, stepped in turn so that every leg sees the same device state; the times are the device events of
 fx_timing.  Legs:
   A  all walls closed, no mask: the planner's solve (several sweeps per launch) -- the yardstick of the step
-  B  Y+ open, no mask: k_jacobi_open_v4 without code bytes (12 bytes per cell and sweep)
-  C  Y+ open, an all-fluid mask: k_jacobi_open_v4 with code bytes (13)
-  D  all walls closed, an all-fluid mask: k_jacobi_obs_v4 (13) -- the yardstick of the sweep
+  B  Y+ open, no mask: k_jacobi_bnd_v4<CODE = 0, OPEN = 1>, no code bytes (12 bytes per cell and sweep)
+  C  Y+ open, an all-fluid mask: k_jacobi_bnd_v4<1, 1> with code bytes (13)
+  D  all walls closed, an all-fluid mask: k_jacobi_bnd_v4<1, 0> (13) -- the yardstick of the sweep
 Every repeat prints one line per leg: us per sweep (jacobi_ms / jacobi_sweeps) and the step in ms.  Then the inflow stage alone:
 fx_open_inflow --stage-reps times on leg B's context with one face open and with all six, us per launch, on the state the steps left.
 """
