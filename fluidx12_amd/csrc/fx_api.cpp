@@ -399,28 +399,40 @@ int fx_advect(fx_ctx* ctx, void* stream)
 	return advect_range(ctx, s, owned(ctx), false);
 }
 
+// ---- the optional stages of the step: vorticity confinement, emitters, obstacles, open walls, buoyancy ------------------------------
+// Their calls want a context that simulates and, unless `whole` is false (the getters), holds the whole grid: FX_E_INVALID for null, FX_E_STATE for a render-only one,
+// FX_E_INVALID for a slab or a rank of a chain -- each stage would need halo planes of its own there (the confinement two of velocity[1] across
+// each face, the temperature a field's worth; the colour halos leave right behind the advection, in front of the passes that change it).
+// A context never fails both of the last two tests: fx_create refuses a render-only slab, check_slab_chain a whole grid in a chain.
+static int sim_guard(const fx_ctx* ctx, bool whole = true)
+{
+	if (!ctx) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (whole && (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1)) return FX_E_INVALID;
+	return FX_OK;
+}
+
+// fx_<stage>(ctx, stream): the stage's phase of the step (fx_schedule.cpp) on its own
+static int run_stage(fx_ctx* ctx, void* stream, int (*phase)(fx_ctx*, hipStream_t))
+{
+	const int rc = sim_guard(ctx);
+	return rc ? rc : phase(ctx, pick_stream(ctx, stream));
+}
+
 int fx_set_vorticity_confinement(fx_ctx* ctx, float epsilon)
 {
-	if (!ctx || !std::isfinite(epsilon) || epsilon < 0.0f) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // a slab would need two planes of velocity[1] across each face
+	if (!std::isfinite(epsilon) || epsilon < 0.0f) return FX_E_INVALID;
+	if (const int rc = sim_guard(ctx)) return rc;
 	ctx->vort_eps = epsilon;
 	return FX_OK;
 }
 
-int fx_confine_vorticity(fx_ctx* ctx, void* stream)
-{
-	if (!ctx || ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	return confine_phase(ctx, pick_stream(ctx, stream));
-}
+int fx_confine_vorticity(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, confine_phase); }
 
 int fx_set_emitters(fx_ctx* ctx, const fx_emitter* list, uint32_t count)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;          // (before every other test: the header promises it for all four calls)
+	if (const int rc = sim_guard(ctx)) return rc;
 	if (count > FX_MAX_EMITTERS || (count && !list)) return FX_E_INVALID;
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: the colour halos leave right behind the advection
 	for (uint32_t k = 0; k < count; ++k) {
 		const fx_emitter& e = list[k];
 		if (e.struct_size != sizeof(fx_emitter) || e.flags != 0) return FX_E_INVALID;
@@ -434,8 +446,7 @@ int fx_set_emitters(fx_ctx* ctx, const fx_emitter* list, uint32_t count)
 
 int fx_get_emitters(fx_ctx* ctx, fx_emitter* out, uint32_t capacity, uint32_t* count)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx, false)) return rc;             // (slab ranks may ask: the list is empty there)
 	if (!count || (capacity && !out)) return FX_E_INVALID;
 	*count = (uint32_t)ctx->emitters.size();
 	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->emitters[k];
@@ -444,28 +455,18 @@ int fx_get_emitters(fx_ctx* ctx, fx_emitter* out, uint32_t capacity, uint32_t* c
 
 int fx_set_impulse(fx_ctx* ctx, int enabled)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (!enabled && (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1)) return FX_E_INVALID;   // on the emitters' footing: without it a slab rank has no source
+	if (const int rc = sim_guard(ctx, !enabled)) return rc;           // off: on the emitters' footing -- without it a slab rank has no source
 	ctx->impulse_on = enabled != 0;
 	return FX_OK;
 }
 
-int fx_emit(fx_ctx* ctx, void* stream)
-{
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
-	return emit_phase(ctx, pick_stream(ctx, stream));
-}
+int fx_emit(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, emit_phase); }
 
 // ---- solid obstacles (fx_obstacle.hip) ------------------------------------------------------------------
 int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t bytes, uint32_t flags)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx)) return rc;
 	if (flags & ~(uint32_t)FX_OBSTACLES_DEVICE) return FX_E_INVALID;
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the confinement's footing
 	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no obstacle-aware kernels
 	DeviceGuard dg(ctx->device);
 	if (!solid) {                                                           // detach: every launch is the plain one again
@@ -505,8 +506,7 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 
 int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx, false)) return rc;
 	const size_t n = ctx->g.plane() * (size_t)ctx->g.Zg;
 	if (solid_out && bytes != n) return FX_E_INVALID;
 	if (solid_cells) *solid_cells = ctx->obst_code ? ctx->obst_cells : 0;
@@ -522,22 +522,13 @@ int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* so
 	return FX_OK;
 }
 
-int fx_enforce_obstacles(fx_ctx* ctx, void* stream)
-{
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
-	return enforce_phase(ctx, pick_stream(ctx, stream));
-}
+int fx_enforce_obstacles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, enforce_phase); }
 
 // ---- open walls (fx_open.hip) ---------------------------------------------------------------------------
 int fx_set_open_walls(fx_ctx* ctx, uint32_t faces)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (faces & ~0x3Fu) return FX_E_INVALID;
-	if (ctx->g.Zg <= 1 && (faces & (FX_WALL_Z_LO | FX_WALL_Z_HI))) return FX_E_INVALID;   // a 2-D grid has no z faces
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the obstacles' footing
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (!open_faces_ok(ctx->g, faces)) return FX_E_INVALID;                 // (a 2-D grid has no z faces)
 	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no open-wall kernels
 	ctx->open_faces = faces;
 	return FX_OK;
@@ -545,26 +536,18 @@ int fx_set_open_walls(fx_ctx* ctx, uint32_t faces)
 
 int fx_get_open_walls(fx_ctx* ctx, uint32_t* faces)
 {
-	if (!ctx || !faces) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (!faces) return FX_E_INVALID;
+	if (const int rc = sim_guard(ctx, false)) return rc;
 	*faces = ctx->open_faces;
 	return FX_OK;
 }
 
-int fx_open_inflow(fx_ctx* ctx, void* stream)
-{
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
-	return open_inflow_phase(ctx, pick_stream(ctx, stream));
-}
+int fx_open_inflow(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, open_inflow_phase); }
 
 // ---- buoyancy (fx_heat.hip) -------------------------------------------------------------------------------
 int fx_set_buoyancy(fx_ctx* ctx, const fx_buoyancy* b)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;     // slab ranks: on the confinement's footing (the field would need halo planes of its own)
+	if (const int rc = sim_guard(ctx)) return rc;
 	DeviceGuard dg(ctx->device);
 	if (!b) {                                                               // off: every call behaves as without this function, the field goes
 		for (int i = 0; i < 2; ++i) {
@@ -607,8 +590,7 @@ int fx_set_buoyancy(fx_ctx* ctx, const fx_buoyancy* b)
 
 int fx_get_buoyancy(fx_ctx* ctx, fx_buoyancy* out, int* enabled)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx, false)) return rc;
 	if (out) *out = ctx->buoy;
 	if (enabled) *enabled = ctx->buoy_on ? 1 : 0;
 	return FX_OK;
@@ -616,10 +598,8 @@ int fx_get_buoyancy(fx_ctx* ctx, fx_buoyancy* out, int* enabled)
 
 int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx)) return rc;
 	if (count > FX_MAX_HEAT_SOURCES || (count && !list)) return FX_E_INVALID;
-	if (ctx->g.nz != ctx->g.Zg || ctx->nranks > 1) return FX_E_INVALID;
 	for (uint32_t k = 0; k < count; ++k) {
 		const fx_heat_source& e = list[k];
 		if (e.struct_size != sizeof(fx_heat_source) || e.flags != 0) return FX_E_INVALID;
@@ -632,21 +612,14 @@ int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count)
 
 int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uint32_t* count)
 {
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	if (const int rc = sim_guard(ctx, false)) return rc;
 	if (!count || (capacity && !out)) return FX_E_INVALID;
 	*count = (uint32_t)ctx->heat_sources.size();
 	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->heat_sources[k];
 	return FX_OK;
 }
 
-int fx_heat(fx_ctx* ctx, void* stream)
-{
-	if (!ctx) return FX_E_INVALID;
-	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
-	if (ctx->nranks > 1 || ctx->g.nz != ctx->g.Zg) return FX_E_INVALID;
-	return heat_phase(ctx, pick_stream(ctx, stream));
-}
+int fx_heat(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, heat_phase); }
 
 int fx_divergence(fx_ctx* ctx, void* stream)
 {

@@ -24,53 +24,17 @@
 // When the step's advection wrote the render's alpha side volume (fx_render_accel.hip), the pass stores the stored alpha of every cell it
 // changes there too, so the volume stays true to the colour field.
 #include "fx_internal.h"
+#include "fx_store.h"
 
 namespace fx {
 
-namespace {
+using namespace sto;
 
-typedef _Float16 h16;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 const int ET_X = kEmitTileX, ET_Y = kEmitTileY;  // tile: one wave a row
 
 __device__ __forceinline__ float saturatef(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-// the fp32 value is rounded to binary16 in a step of its own (RNE): the empty asm keeps the producing FMA and the conversion apart
-// (the same device as Store<true> of fx_sim.hip)
-__device__ __forceinline__ h16 to_h16(float v) { asm("" : "+v"(v)); return (h16)v; }
-
-// WIDE: fields of 4 GiB and more -- 64-bit byte offsets; otherwise 32-bit ones from uniform bases (saddr + voffset accesses)
-template <bool WIDE> struct Off { typedef uint32_t T; };
-template <> struct Off<true> { typedef size_t T; };
-
-template <bool HALF> struct Cell;
-template <> struct Cell<false> {
-	template <typename O> static __device__ __forceinline__ float lds(const char* b, O cell) { return *reinterpret_cast<const float*>(b + cell * (O)4); }
-	template <typename O> static __device__ __forceinline__ void sts(char* b, O cell, float v) { *reinterpret_cast<float*>(b + cell * (O)4) = v; }
-	template <typename O> static __device__ __forceinline__ float4 ldv(const char* b, O cell) { return *reinterpret_cast<const float4*>(b + cell * (O)16); }
-	// stores the texel, returns the alpha a later load of it yields
-	template <typename O> static __device__ __forceinline__ float stv(char* b, O cell, const float (&c)[4])
-	{
-		*reinterpret_cast<float4*>(b + cell * (O)16) = make_float4(c[0], c[1], c[2], c[3]);
-		return c[3];
-	}
-};
-template <> struct Cell<true> {
-	template <typename O> static __device__ __forceinline__ float lds(const char* b, O cell) { return (float)*reinterpret_cast<const h16*>(b + cell * (O)2); }
-	template <typename O> static __device__ __forceinline__ void sts(char* b, O cell, float v) { *reinterpret_cast<h16*>(b + cell * (O)2) = to_h16(v); }
-	template <typename O> static __device__ __forceinline__ float4 ldv(const char* b, O cell)
-	{
-		const h16x4 h = *reinterpret_cast<const h16x4*>(b + cell * (O)8);
-		return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-	}
-	template <typename O> static __device__ __forceinline__ float stv(char* b, O cell, const float (&c)[4])
-	{
-		h16x4 h;
-		h.x = to_h16(c[0]); h.y = to_h16(c[1]); h.z = to_h16(c[2]); h.w = to_h16(c[3]);
-		*reinterpret_cast<h16x4*>(b + cell * (O)8) = h;
-		return (float)h.w;
-	}
-};
 
 }  // namespace
 
@@ -106,8 +70,8 @@ __global__ __launch_bounds__(256) void k_emit(const Geom g, const EmitArgs a, vo
 	const O id = (O)g.lz(z) * (O)g.plane() + (O)y * (O)g.X + (O)x;
 	char* v0 = static_cast<char*>(vel);
 	char* co = static_cast<char*>(col);
-	float u[3] = { Ce::lds(v0, id), Ce::lds(v0, stride + id), Ce::lds(v0, (O)2 * stride + id) };
-	const float4 c4 = Ce::ldv(co, id);
+	float u[3] = { Ce::ld1(v0, id), Ce::ld1(v0, stride + id), Ce::ld1(v0, (O)2 * stride + id) };
+	const float4 c4 = Ce::ld4(co, id);
 	float c[4] = { c4.x, c4.y, c4.z, c4.w };
 
 	const float px = ((float)x + 0.5f) / (float)g.X;            // Simulation.hlsli:10, as k_advect
@@ -141,23 +105,23 @@ __global__ __launch_bounds__(256) void k_emit(const Geom g, const EmitArgs a, vo
 		}
 	}
 	if (!changed) return;                                       // outside every support: the cell keeps its bits
-	Ce::sts(v0, id, u[0]);
-	Ce::sts(v0, stride + id, u[1]);
-	Ce::sts(v0, (O)2 * stride + id, u[2]);
-	const float stored_alpha = Ce::stv(co, id, c);
+	Ce::st1(v0, id, u[0]);
+	Ce::st1(v0, stride + id, u[1]);
+	Ce::st1(v0, (O)2 * stride + id, u[2]);
+	const float stored_alpha = Ce::st4(co, id, c);
 	if (alpha) *reinterpret_cast<float*>(reinterpret_cast<char*>(alpha) + id * (O)4) = stored_alpha;
 }
 
 hipError_t launch_emit(const Geom& g, int half_store, void* vel, void* col, float* alpha, const fx_emitter* list, int count, float dt, hipStream_t s)
 {
-	if (g.nz != g.Zg || g.H != 0) return hipErrorNotSupported;                  // whole grids only (fx_set_emitters refuses slab ranks)
+	if (!whole_grid(g)) return hipErrorNotSupported;                            // (fx_set_emitters refuses slab ranks)
 	EmitArgs a;
 	const int wgs = emit_plan(g, list, count, &a);
 	if (wgs < 0) return hipErrorInvalidValue;
 	if (wgs == 0) return hipSuccess;                                            // every box clipped away: nothing to launch
 	const dim3 grid((unsigned)wgs, 1, 1), block(ET_X, ET_Y, 1);
 	const int is3d = g.Zg > 1 ? 1 : 0;
-	const bool wide = g.cells_local() * 16 >= ((size_t)1 << 32);
+	const bool wide = colour_wants_wide_offsets(g);
 	if (half_store) {
 		if (wide) hipLaunchKernelGGL((k_emit<true, true>), grid, block, 0, s, g, a, vel, col, alpha, dt, is3d);
 		else hipLaunchKernelGGL((k_emit<true, false>), grid, block, 0, s, g, a, vel, col, alpha, dt, is3d);

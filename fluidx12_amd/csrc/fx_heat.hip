@@ -22,35 +22,17 @@
 // compares, and a wave whose lanes are all far below the threshold skips the transcendental, as k_emit does.  The axes the force acts on
 // are a launch-uniform argument: a component with up[a] == 0 is neither read nor written.
 #include "fx_internal.h"
+#include "fx_store.h"
 
 namespace fx {
 
-namespace {
+using namespace sto;
 
-typedef _Float16 h16;
+namespace {
 
 const int HT_X = kHeatTileX, HT_Y = kHeatTileY;
 
-// the fp32 value is rounded to binary16 in a step of its own (RNE): the empty asm keeps the producing FMA and the conversion apart
-// (the device of fx_emit.hip, restated)
-__device__ __forceinline__ h16 to_h16(float v) { asm("" : "+v"(v)); return (h16)v; }
-
-template <bool WIDE> struct Off { typedef uint32_t T; };
-template <> struct Off<true> { typedef size_t T; };
-
-// velocity components and the colour texel's alpha, by cell index from a byte base
-template <bool HALF> struct Cell;
-template <> struct Cell<false> {
-	template <typename O> static __device__ __forceinline__ float lds(const char* b, O cell) { return *reinterpret_cast<const float*>(b + cell * (O)4); }
-	template <typename O> static __device__ __forceinline__ void sts(char* b, O cell, float v) { *reinterpret_cast<float*>(b + cell * (O)4) = v; }
-	template <typename O> static __device__ __forceinline__ float alpha(const char* b, O cell) { return *reinterpret_cast<const float*>(b + cell * (O)16 + (O)12); }
-};
-template <> struct Cell<true> {
-	template <typename O> static __device__ __forceinline__ float lds(const char* b, O cell) { return (float)*reinterpret_cast<const h16*>(b + cell * (O)2); }
-	template <typename O> static __device__ __forceinline__ void sts(char* b, O cell, float v) { *reinterpret_cast<h16*>(b + cell * (O)2) = to_h16(v); }
-	template <typename O> static __device__ __forceinline__ float alpha(const char* b, O cell) { return (float)*reinterpret_cast<const h16*>(b + cell * (O)8 + (O)6); }
-};
-
+// the temperature, fp32 in every context
 template <typename O> __device__ __forceinline__ float ldt(const char* b, O cell) { return *reinterpret_cast<const float*>(b + cell * (O)4); }
 
 __device__ __forceinline__ float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
@@ -105,7 +87,7 @@ __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, co
 	const float pz = ((float)z + 0.5f) / (float)g.Zg;
 	// (2-D grids load u0z and form fz too, on purpose: the z lerp on equal operands below is k_advect's, with its NaN / inf / -0 behaviour -- one
 	// load per cell more than the bytes-per-cell floor of the 3-D pass counts)
-	const float u0x = Ce::lds(v0, id), u0y = Ce::lds(v0, stride + id), u0z = Ce::lds(v0, (O)2 * stride + id);
+	const float u0x = Ce::ld1(v0, id), u0y = Ce::ld1(v0, stride + id), u0z = Ce::ld1(v0, (O)2 * stride + id);
 	const float ax = fmaf(-u0x, dt, px), ay = fmaf(-u0y, dt, py), az = fmaf(-u0z, dt, pz);
 	const float tx = ax * (float)g.X - 0.5f, ty = ay * (float)g.Y - 0.5f, tz = az * (float)g.Zg - 0.5f;
 	const float flx = floorf(tx), fly = floorf(ty), flz = floorf(tz);
@@ -157,9 +139,9 @@ __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, co
 	// ---- 6: the force, on the axes with up != 0
 	const float rho = Ce::alpha(static_cast<const char*>(col), id);
 	const float s = fmaf(a.lift, T1 - Ta, -(a.weight * rho));
-	if (a.axes & 1) Ce::sts(v1, id, fmaf(a.up[0] * s, dt, Ce::lds(v1, id)));
-	if (a.axes & 2) Ce::sts(v1, stride + id, fmaf(a.up[1] * s, dt, Ce::lds(v1, stride + id)));
-	if (IS3D && (a.axes & 4)) Ce::sts(v1, (O)2 * stride + id, fmaf(a.up[2] * s, dt, Ce::lds(v1, (O)2 * stride + id)));
+	if (a.axes & 1) Ce::st1(v1, id, fmaf(a.up[0] * s, dt, Ce::ld1(v1, id)));
+	if (a.axes & 2) Ce::st1(v1, stride + id, fmaf(a.up[1] * s, dt, Ce::ld1(v1, stride + id)));
+	if (IS3D && (a.axes & 4)) Ce::st1(v1, (O)2 * stride + id, fmaf(a.up[2] * s, dt, Ce::ld1(v1, (O)2 * stride + id)));
 }
 
 template <bool HALF, bool IS3D>
@@ -174,14 +156,14 @@ static hipError_t launch_heat_t(bool wide, dim3 grid, dim3 block, hipStream_t s,
 hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
 	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s, unsigned faces)
 {
-	if (g.nz != g.Zg || g.H != 0) return hipErrorNotSupported;                  // whole grids only (fx_set_buoyancy refuses slab ranks)
+	if (!whole_grid(g)) return hipErrorNotSupported;                            // (fx_set_buoyancy refuses slab ranks)
 	if (!vel0 || !vel1 || !col || !t_in || !t_out || t_in == t_out) return hipErrorInvalidValue;
-	if ((faces & ~0x3Fu) || (g.Zg <= 1 && (faces & 0x30u))) return hipErrorInvalidValue;
+	if (!open_faces_ok(g, faces)) return hipErrorInvalidValue;
 	HeatArgs a;
 	const int wgs = heat_plan(g, b, list, count, &a);
 	if (wgs <= 0) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)wgs, 1, 1), block(HT_X, HT_Y, 1);
-	const bool wide = g.cells_local() * 16 >= ((size_t)1 << 32);                // the colour field, the largest one, in fp32
+	const bool wide = colour_wants_wide_offsets(g);
 	const bool is3d = g.Zg > 1;
 	if (half_store) return is3d ? launch_heat_t<true, true>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces)
 	                            : launch_heat_t<true, false>(wide, grid, block, s, g, a, vel0, vel1, col, t_in, t_out, code, dt, address, faces);

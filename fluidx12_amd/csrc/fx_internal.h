@@ -25,6 +25,13 @@ struct Geom {
 	// local plane index of global plane z (must be present)
 	__host__ __device__ int lz(int z) const { return z - z0 + H; }
 };
+// ---- what the launchers of the step's optional stages (vorticity, emitters, obstacles, buoyancy, open walls) test, host side
+// the geometry is a whole grid, no slab of one: those stages refuse anything else with hipErrorNotSupported (local plane = global plane)
+inline bool whole_grid(const Geom& g) { return g.nz == g.Zg && g.H == 0; }
+// faces holds FX_WALL_* bits only, and no z face on a 2-D grid
+inline bool open_faces_ok(const Geom& g, unsigned faces) { return !(faces & ~0x3Fu) && !(g.Zg <= 1 && (faces & (FX_WALL_Z_LO | FX_WALL_Z_HI))); }
+// the colour field, the largest one, takes 4 GiB or more in fp32: the kernels that address by byte offset need 64-bit ones (WIDE, fx_store.h)
+inline bool colour_wants_wide_offsets(const Geom& g) { return g.cells_local() * 16 >= ((size_t)1 << 32); }
 
 // frame constants of the ray-march kernels (Common.hlsli:15-30 cbPerObject/cbPerFrame)
 struct FrameConsts {

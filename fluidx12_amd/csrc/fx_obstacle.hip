@@ -25,33 +25,15 @@
 // kernels' association order; fp16 storage widens on load and rounds once (RNE) on store.
 // Whole grids only (fx_set_obstacles and fx_set_open_walls refuse slab ranks): local plane = global plane.
 #include "fx_internal.h"
+#include "fx_store.h"
 
 namespace fx {
 
+using namespace sto;
+
 namespace {
 
-typedef _Float16 h16;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
 enum { OB_XM = 1, OB_XP = 2, OB_YM = 4, OB_YP = 8, OB_ZM = 16, OB_ZP = 32, OB_SELF = 64 };
-
-// velocity / colour storage: fp32, or binary16 rounded from the fp32 result in a step of its own (the empty asm keeps the producing
-// multiply and the conversion apart -- the same device as Store<true> of fx_sim.hip)
-template <bool HALF> struct Sto;
-template <> struct Sto<false> {
-	typedef float S;
-	typedef float4 S4;
-	static __device__ __forceinline__ float ld(const S* p, size_t i) { return p[i]; }
-	static __device__ __forceinline__ void st(S* p, size_t i, float v) { p[i] = v; }
-	static __device__ __forceinline__ void zero4(S4* p, size_t i) { p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-};
-template <> struct Sto<true> {
-	typedef h16 S;
-	typedef h16x4 S4;
-	static __device__ __forceinline__ float ld(const S* p, size_t i) { return (float)p[i]; }
-	static __device__ __forceinline__ void st(S* p, size_t i, float v) { asm("" : "+v"(v)); p[i] = (h16)v; }
-	static __device__ __forceinline__ void zero4(S4* p, size_t i) { h16x4 h; h.x = h.y = h.z = h.w = (h16)0.0f; p[i] = h; }
-};
 
 // workgroup -> tile, the mapping of the plain kernels (fx_sim.hip xcd_tile): remap 1 = XCD k walks the k-th contiguous eighth of the
 // (x, y, z)-ordered tile sequence, 0 = natural order.  Speed only.
@@ -369,7 +351,6 @@ __global__ __launch_bounds__(256) void k_project_bnd(const Geom g, const SimPara
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-static inline bool whole_grid(const Geom& g) { return g.nz == g.Zg && g.H == 0; }
 static inline dim3 grid_cells(const Geom& g, int nzp) { return dim3(((g.X + 63) / 64) * ((g.Y + 3) / 4) * nzp, 1, 1); }
 // the plain kernels' defaults (fx_sim.hip xcd_remap_for): the sweeps always take the contiguous-eighth order, divergence and projection on
 // the small 3-D grids that live in L2
@@ -427,11 +408,10 @@ hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel,
 }
 
 // ---- the bnd family.  code may be null (open walls alone), faces may be 0 (obstacles in a closed box); not both: those are the plain kernels
-static inline bool faces_ok(const Geom& g, unsigned faces) { return !(faces & ~0x3Fu) && !(g.Zg <= 1 && (faces & (OB_ZM | OB_ZP))); }
 static inline hipError_t bnd_args(const Geom& g, const uint8_t* code, unsigned faces, int z_begin, int z_end)
 {
 	if (!whole_grid(g)) return hipErrorNotSupported;
-	return faces_ok(g, faces) && (code || faces) && z_begin >= 0 && z_end <= g.Zg ? hipSuccess : hipErrorInvalidValue;
+	return open_faces_ok(g, faces) && (code || faces) && z_begin >= 0 && z_end <= g.Zg ? hipSuccess : hipErrorInvalidValue;
 }
 // the wide sweep.  OBSTACLE_V4 = 0 (lab builds): the scalar kernel on every geometry -- what tests/test_gpu_obstacles.py and
 // tests/test_gpu_open_walls.py hold the wide one against

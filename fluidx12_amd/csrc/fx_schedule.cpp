@@ -281,6 +281,10 @@ int advect_all(fx_ctx* ctx, std::vector<fx_ctx*>& M, hipStream_t s)
 	return FX_OK;
 }
 
+// The render's alpha side volume (fx_render_accel.hip) if this step's advection left the alpha of colour[parity] in it, else null: a pass that
+// changes that colour field in place stores the alpha there too, so the volume stays true.
+static float* alpha_mirror(const fx_ctx* ctx) { return ctx->accel_alpha_of == ctx->col[ctx->frame_parity] ? ctx->accel.alpha : nullptr; }
+
 // Vorticity confinement (fx_vorticity.hip) finishes the advected velocity, so its time is booked with the advection.  The pass cannot run
 // in place; velocity[0] is dead between the advection and the projection of a single domain, so the result goes there and the two
 // pointers swap: velocity[1] then names the confined field, the projection overwrites the other buffer as always.  Everybody who holds
@@ -306,9 +310,7 @@ int open_inflow_phase(fx_ctx* ctx, hipStream_t s)
 	if (!ctx->open_faces || !(ctx->time_step > 0.0f)) return FX_OK;
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_ADVECT);
-	const int par = ctx->frame_parity;
-	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
-	FX_HIP(launch_open_inflow(ctx->g, ctx->half, ctx->vel[0], ctx->col[par], alpha, ctx->open_faces, ctx->time_step, s));
+	FX_HIP(launch_open_inflow(ctx->g, ctx->half, ctx->vel[0], ctx->col[ctx->frame_parity], alpha_mirror(ctx), ctx->open_faces, ctx->time_step, s));
 	return FX_OK;
 }
 
@@ -320,9 +322,7 @@ int emit_phase(fx_ctx* ctx, hipStream_t s)
 	if (ctx->emitters.empty() || !(ctx->time_step > 0.0f)) return FX_OK;
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_ADVECT);
-	const int par = ctx->frame_parity;
-	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
-	FX_HIP(launch_emit(ctx->g, ctx->half, ctx->vel[1], ctx->col[par], alpha, ctx->emitters.data(), (int)ctx->emitters.size(), ctx->time_step, s));
+	FX_HIP(launch_emit(ctx->g, ctx->half, ctx->vel[1], ctx->col[ctx->frame_parity], alpha_mirror(ctx), ctx->emitters.data(), (int)ctx->emitters.size(), ctx->time_step, s));
 	return FX_OK;
 }
 
@@ -350,9 +350,7 @@ int enforce_phase(fx_ctx* ctx, hipStream_t s)
 	if (!ctx->obst_code || !ctx->obst_cells || !(ctx->time_step > 0.0f)) return FX_OK;
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_ADVECT);
-	const int par = ctx->frame_parity;
-	float* alpha = ctx->accel_alpha_of == ctx->col[par] ? ctx->accel.alpha : nullptr;
-	FX_HIP(launch_obstacle_enforce(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->vel[1], ctx->col[par], alpha, s));
+	FX_HIP(launch_obstacle_enforce(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->vel[1], ctx->col[ctx->frame_parity], alpha_mirror(ctx), s));
 	return FX_OK;
 }
 
@@ -713,6 +711,12 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// The optional stages between the advection and the divergence, each a no-op unless its feature is set (whole-grid contexts only: the setters
+// refuse slab ranks).  The order is the contract, every phase's own comment gives its half of it: the inflow pass scales what the advection
+// sampled, before the emitters add to it; buoyancy reads the alpha the emitters added; the enforce pass clears the solid cells of everything
+// added so far; the confinement comes last because it writes into velocity[0], the field the inflow pass and buoyancy trace with.
+static int (*const kOptionalStages[])(fx_ctx*, hipStream_t) = { open_inflow_phase, emit_phase, heat_phase, enforce_phase, confine_phase };
+
 int simulate_impl(fx_ctx* ctx, hipStream_t s)
 {
 	std::vector<fx_ctx*> M;
@@ -729,11 +733,8 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		for (fx_ctx* m : M) m->col_halo_buf = (int)m->frame_parity;
 	}
 	if (ctx->time_step > 0.0f) {                       // CSProject3D.hlsl:88
-		for (fx_ctx* m : M) if ((rc = open_inflow_phase(m, CS(m, s)))) return rc;  // (whole-grid contexts with an open wall only)
-		for (fx_ctx* m : M) if ((rc = emit_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with emitters set only)
-		for (fx_ctx* m : M) if ((rc = heat_phase(m, CS(m, s)))) return rc;         // (whole-grid contexts with buoyancy on only)
-		for (fx_ctx* m : M) if ((rc = enforce_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with obstacles set only)
-		for (fx_ctx* m : M) if ((rc = confine_phase(m, CS(m, s)))) return rc;      // (whole-grid contexts with epsilon > 0 only)
+		for (const auto stage : kOptionalStages)
+			for (fx_ctx* m : M) if ((rc = stage(m, CS(m, s)))) return rc;
 		const ExchSpec uz{ EX_UZ1, 1, 0 };
 		if ((rc = do_exchange(ctx, M, &uz, 1, ON_COMPUTE, s))) return rc;
 		if (takes_sparse_solver(ctx, ctx->desc.jacobi_iters) && jacobi_freeze_can_fuse_divergence(ctx->g)) ctx->fz_fuse_div = true;   // k_freeze_dense computes it

@@ -23,12 +23,13 @@
 // wall cell it clamps to (read by nobody).  Every velocity component is read from HBM once (+ rim and chunk overlap, mostly L2) and
 // written once.  Rows of any length: lanes beyond the row clamp their reads and store nothing.
 #include "fx_internal.h"
+#include "fx_store.h"
 
 namespace fx {
 
-namespace {
+using namespace sto;
 
-typedef _Float16 vh16;
+namespace {
 
 const int VT_X = 64, VT_Y = 16;                 // tile
 const int VU_W = VT_X + 4, VU_H = VT_Y + 4;     // velocity planes of the ring: 2-cell rim
@@ -38,20 +39,6 @@ const int VLD = (VU_N + 255) / 256;             // ring positions a thread fills
 const int VROWS = VT_Y / 4;                     // own cells per thread (rows ty, ty + 4, ...)
 const int VRIM = VM_W * VM_H - VT_X * VT_Y;     // rim positions of an m plane (164)
 
-template <bool HALF> struct VStore;
-template <> struct VStore<false> {
-	typedef float S;
-	static __device__ __forceinline__ float ld(const S* p, size_t i) { return p[i]; }
-	static __device__ __forceinline__ void st(S* p, size_t i, float v) { p[i] = v; }
-};
-template <> struct VStore<true> {
-	typedef vh16 S;
-	static __device__ __forceinline__ float ld(const S* p, size_t i) { return (float)p[i]; }
-	// the fp32 sum is rounded to binary16 in a step of its own (RNE): the empty asm keeps the compiler from folding the add and the
-	// conversion into one mixed-precision instruction that rounds once (the same device as Store<true> of fx_sim.hip)
-	static __device__ __forceinline__ void st(S* p, size_t i, float v) { asm("" : "+v"(v)); p[i] = (vh16)v; }
-};
-
 __device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
 
 struct Vec3 { float x, y, z; };
@@ -59,10 +46,10 @@ struct Vec3 { float x, y, z; };
 }  // namespace
 
 template <bool HALF, bool IS3D>
-__global__ __launch_bounds__(256) void k_vorticity(const Geom g, const typename VStore<HALF>::S* __restrict__ vin,
-	typename VStore<HALF>::S* __restrict__ vout, float eps, float dt, int zchunk, int tiles_x, int tiles_y)
+__global__ __launch_bounds__(256) void k_vorticity(const Geom g, const typename Sto<HALF>::S* __restrict__ vin,
+	typename Sto<HALF>::S* __restrict__ vout, float eps, float dt, int zchunk, int tiles_x, int tiles_y)
 {
-	typedef VStore<HALF> St;
+	typedef Sto<HALF> St;
 	constexpr int NC = IS3D ? 3 : 2;            // components the stencil reads (2-D: uz is only copied)
 	constexpr int NP = IS3D ? 3 : 1;            // planes of the rings
 	__shared__ float su[NP][NC][VU_N];
@@ -213,7 +200,7 @@ __global__ __launch_bounds__(256) void k_vorticity(const Geom g, const typename 
 
 hipError_t launch_confine_vorticity(const Geom& g, int half_store, const void* vel_in, void* vel_out, float eps, float dt, hipStream_t s)
 {
-	if (g.nz != g.Zg || g.H != 0) return hipErrorNotSupported;                  // whole grids only: a slab would need two planes across each face
+	if (!whole_grid(g)) return hipErrorNotSupported;                            // a slab would need two planes across each face
 	const int tiles_x = (g.X + VT_X - 1) / VT_X, tiles_y = (g.Y + VT_Y - 1) / VT_Y;
 	const long long tiles = (long long)tiles_x * tiles_y;
 	const bool is3d = g.Zg > 1;
@@ -227,7 +214,6 @@ hipError_t launch_confine_vorticity(const Geom& g, int half_store, const void* v
 	}
 	if (tiles * nchunks > 0x7fffffffLL) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)(tiles * nchunks), 1, 1), block(256, 1, 1);
-	typedef _Float16 h16;
 	if (is3d) {
 		if (half_store) hipLaunchKernelGGL((k_vorticity<true, true>), grid, block, 0, s, g, (const h16*)vel_in, (h16*)vel_out, eps, dt, zchunk, tiles_x, tiles_y);
 		else hipLaunchKernelGGL((k_vorticity<false, true>), grid, block, 0, s, g, (const float*)vel_in, (float*)vel_out, eps, dt, zchunk, tiles_x, tiles_y);
