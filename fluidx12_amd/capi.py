@@ -29,6 +29,7 @@ OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memo
 MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
 WALL_X_LO, WALL_X_HI, WALL_Y_LO, WALL_Y_HI, WALL_Z_LO, WALL_Z_HI = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20   # FX_WALL_*: fx_set_open_walls
 WALL_ALL = 0x3F
+ADVECT_SEMI_LAGRANGIAN, ADVECT_MACCORMACK = 0, 1   # FX_ADVECT_*: fx_set_advection_scheme
 
 
 class Desc(C.Structure):
@@ -118,6 +119,8 @@ SYMBOLS = {
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),
+    "fx_set_advection_scheme": (C.c_int, [_vp, C.c_uint32]),
+    "fx_get_advection_scheme": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),

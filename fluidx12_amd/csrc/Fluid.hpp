@@ -152,6 +152,11 @@ public:
 	bool GetOpenWalls(uint32_t& faces) { m_status = fx_get_open_walls(m_ctx, &faces); return m_status == FX_OK; }
 	bool OpenInflow(void* stream = nullptr) { m_status = fx_open_inflow(m_ctx, stream); return m_status == FX_OK; }
 
+	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
+	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
+	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }
+	bool GetAdvectionScheme(uint32_t& scheme) { m_status = fx_get_advection_scheme(m_ctx, &scheme); return m_status == FX_OK; }
+
 	// not in the reference (its only lift is the constant force inside its impulse ball): buoyancy -- a temperature advected with the flow that
 	// lifts the smoke, and the smoke's weight (fx_set_buoyancy; nullptr = off, the default) --, its heat sources (fx_set_heat_sources) and the
 	// stage alone (fx_heat), beside Emit.  The field is FX_FIELD_TEMPERATURE while buoyancy is on

@@ -621,6 +621,42 @@ int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uin
 
 int fx_heat(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, heat_phase); }
 
+// ---- the advection scheme (fx_maccormack.hip) ---------------------------------------------------------------
+int fx_set_advection_scheme(fx_ctx* ctx, uint32_t scheme)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (scheme != FX_ADVECT_SEMI_LAGRANGIAN && scheme != FX_ADVECT_MACCORMACK) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	if (scheme == FX_ADVECT_SEMI_LAGRANGIAN) {                                // the default: every launch is the plain one again, the scratch goes
+		if (ctx->mc_vel) FX_HIP(hipFree(ctx->mc_vel));                        // (hipFree waits for the device: nothing reads the scratch any more)
+		ctx->mc_vel = nullptr;
+		if (ctx->mc_col) FX_HIP(hipFree(ctx->mc_col));
+		ctx->mc_col = nullptr;
+		ctx->adv_scheme = scheme;
+		return FX_OK;
+	}
+	if (!ctx->mc_vel) {                                                       // the first successful switch: seven fp32 values per cell
+		const size_t n = ctx->g.cells_owned();
+		float *v = nullptr, *c = nullptr;
+		if (hipMalloc((void**)&v, 3 * n * sizeof(float)) != hipSuccess || hipMalloc((void**)&c, 4 * n * sizeof(float)) != hipSuccess) {
+			(void)hipGetLastError();
+			if (v) (void)hipFree(v);
+			return FX_E_NOMEM;
+		}
+		ctx->mc_vel = v; ctx->mc_col = c;
+	}
+	ctx->adv_scheme = scheme;
+	return FX_OK;
+}
+
+int fx_get_advection_scheme(fx_ctx* ctx, uint32_t* scheme)
+{
+	if (!scheme) return FX_E_INVALID;
+	if (const int rc = sim_guard(ctx, false)) return rc;                     // (slab ranks may ask: semi-Lagrangian there)
+	*scheme = ctx->adv_scheme;
+	return FX_OK;
+}
+
 int fx_divergence(fx_ctx* ctx, void* stream)
 {
 	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;

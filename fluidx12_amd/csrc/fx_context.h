@@ -78,6 +78,12 @@ struct fx_ctx {
 	float* temp[2] = { nullptr, nullptr };
 	int temp_cur = 0;
 	std::vector<fx_heat_source> heat_sources;   // may be set while buoyancy is off; empty = none (default)
+	// the advection scheme (fx_set_advection_scheme; configuration on the same terms): MacCormack's scratch, seven fp32 values per cell whatever the
+	// storage, allocated by the first switch to FX_ADVECT_MACCORMACK and freed by the switch back (fx_maccormack.hip: the predictor writes it, the
+	// corrector reads it; nothing in it outlives a step)
+	uint32_t adv_scheme = FX_ADVECT_SEMI_LAGRANGIAN;
+	float* mc_vel = nullptr;        // three planes of X * Y * Z
+	float* mc_col = nullptr;        // float4 per cell
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -101,6 +101,14 @@ int heat_plan(const Geom& g, const fx_buoyancy& b, const fx_heat_source* list, i
 // faces: the open walls (FX_WALL_* bits, 0 = none): the sample is blended towards the ambient value by open_wall_weight of each axis
 hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, const fx_heat_source* list, int count, const void* vel0, void* vel1,
 	const void* col, const float* t_in, float* t_out, const uint8_t* code, float dt, int address, hipStream_t s, unsigned faces = 0);
+// MacCormack advection (fx_maccormack.hip; fx_set_advection_scheme), two launches over a whole grid: the predictor samples vel_in / col_in at the
+// back-traced place into the scratch (hat_vel: three fp32 planes of X * Y * Z, hat_col: one float4 per cell, fp32 whatever the storage), the
+// corrector samples the scratch at the forward-traced place, corrects, limits to the back-trace's eight taps and finishes like k_advect (impulse,
+// attenuation) into vel_out / col_out.  alpha_out: the render's side volume (it then gets the stored alpha of every cell), or null.
+// hipErrorNotSupported for a slab geometry
+const int kMcTileX = 64, kMcTileY = 4;
+hipError_t launch_maccormack(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const void* col_in, void* vel_out, void* col_out,
+	float* hat_vel, float* hat_col, float* alpha_out, hipStream_t s);
 // ---- open walls (the inflow pass: fx_open.hip; the sweeps and the projection: the bnd launchers below), whole grids only (hipErrorNotSupported
 // for a slab geometry).  faces: FX_WALL_* bits, the code byte's bit order (x-, x+, y-, y+, z-, z+; no z bit on a 2-D grid: hipErrorInvalidValue)
 // The share of a linear sample at t = i0 + f (i0 = fl = floor(t), taps i0 and i0 + 1 of an axis of n cells) that lies inside the box when the

@@ -101,6 +101,20 @@ int advect_range(fx_ctx* ctx, hipStream_t s, Range r, bool own_only)
 	DeviceGuard dg(ctx->device);
 	const SimParams sp{ ctx->time_step, (int)ctx->desc.advect_address, ctx->g.Zg > 1 ? 1 : 0, ctx->impulse_on ? 1 : 0 };
 	const int par = ctx->frame_parity;
+	if (ctx->adv_scheme == FX_ADVECT_MACCORMACK) {
+		// the predictor and the corrector (fx_maccormack.hip) over the whole grid -- fx_set_advection_scheme refuses slab ranks, so the range is
+		// all of it -- from the same inputs into the same outputs as the launch below; the render's alpha side volume on that launch's terms.
+		// Everything behind reads velocity[0] / velocity[1] / colour[parity] per call (the confinement's pointer swap included): the scratch is
+		// the scheme's own and dead once the corrector has run
+		if (!ctx->mc_vel || !ctx->mc_col || r.lo != 0 || r.hi != ctx->g.Zg) { ctx->last_error = "MacCormack advection of a partial plane range"; return FX_E_STATE; }
+		const bool was_rendered = ctx->rendered_since_step && ctx->rendered_on == s;
+		ctx->rendered_since_step = false;
+		float* alpha = was_rendered && ctx->accel_ok && ctx->opt_render_accel && FX_KNOB_INT("ADVECT_ALPHA", 1) ? ctx->accel.alpha : nullptr;
+		if (ctx->accel_alpha_of == ctx->col[par]) ctx->accel_alpha_of = nullptr;      // that buffer is about to change
+		FX_HIP(launch_maccormack(ctx->g, sp, ctx->half, ctx->vel[0], ctx->col[1 - par], ctx->vel[1], ctx->col[par], ctx->mc_vel, ctx->mc_col, alpha, s));
+		if (alpha) ctx->accel_alpha_of = ctx->col[par];
+		return FX_OK;
+	}
 	Geom g = ctx->g;
 	// only halo_advect planes per side were refreshed by EX_ADVECT_IN; the allocation may be wider (max with halo_jacobi), and
 	// a tap into those stale planes must count as "left the exchanged halo", not as present data

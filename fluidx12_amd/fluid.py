@@ -354,6 +354,26 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_open_inflow(self._ctx, stream), "OpenInflow")
 
+    def SetAdvectionScheme(self, scheme):
+        """the advection scheme (fx_set_advection_scheme): "semi-lagrangian" (the reference's, default) or "maccormack" (Selle et al. 2008: a
+        predictor and a corrector launch, second order, limited to the back-trace's taps), or the capi.ADVECT_* value.  Simulate and Advect follow
+        it; the temperature of SetBuoyancy stays semi-Lagrangian.  Configuration: kept across UpdateFrame, not stored in checkpoints (set it
+        again after LoadCheckpoint).  Whole-grid contexts only."""
+        self._need()
+        if isinstance(scheme, str):
+            names = {"semi-lagrangian": capi.ADVECT_SEMI_LAGRANGIAN, "maccormack": capi.ADVECT_MACCORMACK}
+            if scheme.lower() not in names:
+                raise ValueError("unknown advection scheme %r" % (scheme,))
+            scheme = names[scheme.lower()]
+        capi.check(self._lib.fx_set_advection_scheme(self._ctx, int(scheme)), "SetAdvectionScheme")
+
+    def GetAdvectionScheme(self):
+        """the capi.ADVECT_* value in force (fx_get_advection_scheme)"""
+        self._need()
+        scheme = C.c_uint32(0)
+        capi.check(self._lib.fx_get_advection_scheme(self._ctx, C.byref(scheme)), "GetAdvectionScheme")
+        return int(scheme.value)
+
     def SetBuoyancy(self, ambient=0.0, density_weight=0.0, lift=0.0, cooling=0.0, up=(0.0, 1.0, 0.0), flags=0):
         """buoyancy (fx_set_buoyancy): a temperature field advected with the flow, cooling towards `ambient` by max(1 - cooling * dt, 0) per step,
         and the force (-density_weight * COLOR.w + lift * (T - ambient)) * up on VELOCITY1, one pass behind the emitters.  `up` is used as given.

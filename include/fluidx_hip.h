@@ -471,6 +471,41 @@ int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count)
 int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uint32_t* count);
 int fx_heat(fx_ctx* ctx, void* stream);
 
+/* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
+ * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
+ * ch. 30): second order, unconditionally stable with its limiter, two more gathers per cell.  While it is set, the advection of fx_simulate
+ * and the stage call fx_advect run two launches, a predictor and a corrector, in place of the semi-Lagrangian one; the step around them is
+ * unchanged (advect -> inflow -> emit -> heat -> enforce -> confine -> divergence ...).  Per cell (x, y, z), fp32, every operation rounded as
+ * written (tests/maccormack_ref.py restates it in numpy); q ranges over the seven advected quantities VELOCITY x, y, z and COLOR r, g, b, a;
+ * u0 = VELOCITY at the cell, dt = the time step of the last fx_update_frame; fp16 storage widens on load:
+ *   1  the back-trace, tap for tap as the semi-Lagrangian step does it:  p = ((x + .5) / X, (y + .5) / Y, (z + .5) / Z)      a = fma(-u0, dt, p)
+ *      t = a * N - 0.5, i0 = floor(t), f = t - i0 per axis; the eight taps i0, i0 + 1 go through the context's address mode (clamp / mirror);
+ *      hat_q = lerp_z(lerp_y(lerp_x ...)) with lerp(a, b, f) = fma(f, b - a, a).  The bounds go over the eight taps v in the order 000, 100,
+ *      010, 110, 001, 101, 011, 111 (x fastest), starting at the first tap:   lo = v < lo ? v : lo      hi = v > hi ? v : hi
+ *      -- selects, not fmin / fmax: of +0 and -0 the earlier tap stays, a NaN tap never replaces a bound
+ *   2  the predictor stores hat_q (fp32) for all seven quantities into a scratch
+ *   3  the forward trace from the same cell with the same u0:  b = fma(u0, dt, p), taps and fractions as in 1 through the same address mode;
+ *      bar_q = the same trilinear sample, taken from the scratch
+ *   4  r_q = fma(0.5, q - bar_q, hat_q), q the cell's own stored value;   then the limiter  r_q = r_q < lo ? lo : (r_q > hi ? hi : r_q)
+ *   5  the tail of the semi-Lagrangian step, unchanged, on r: the built-in impulse unless fx_set_impulse switched it off, the attenuation
+ *      max(fma(-dt, 0.2, 1), 0), the stores into VELOCITY1 and COLOR, each rounded once, and the render's alpha side volume on the
+ *      semi-Lagrangian step's own condition
+ * No special cases: dt <= 0 and 2-D grids go through the same rules (a 2-D grid: both z taps are plane 0, the z lerp runs on equal operands).
+ * The temperature of fx_set_buoyancy stays semi-Lagrangian under either scheme.
+ * fx_set_advection_scheme: FX_ADVECT_SEMI_LAGRANGIAN is the default: every call behaves exactly as without this function.  The first
+ * successful switch to FX_ADVECT_MACCORMACK allocates the scratch, seven fp32 values per cell (three planes of X * Y * Z and one float4
+ * volume) whatever fx_desc.storage is -- FX_E_NOMEM if that fails, the scheme staying as it was; the switch back frees it.  The scratch
+ * carries nothing from step to step.  Configuration like the emitters: per context, kept across fx_update_frame, not checkpointed (a resumed
+ * run only has to set the scheme again behind fx_checkpoint_load), not part of fx_field_digest.  FX_E_INVALID, the previous setting staying
+ * in force: an unknown scheme, a NULL ctx or out-pointer, and (the setter) a context that owns fewer planes than the grid -- slab ranks of
+ * every transport: the corrector would need halo planes of the predicted fields.  FX_E_STATE (both calls): FX_FLAG_RENDER_ONLY contexts.
+ * Both Jacobi modes, both address modes, both storages, 2-D grids and every optional stage are served.
+ * Timing: both launches are booked into fx_timing.advect_ms. */
+#define FX_ADVECT_SEMI_LAGRANGIAN 0u   /* the reference's CSAdvect; the default */
+#define FX_ADVECT_MACCORMACK      1u
+int fx_set_advection_scheme(fx_ctx* ctx, uint32_t scheme);
+int fx_get_advection_scheme(fx_ctx* ctx, uint32_t* scheme);
+
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
 int fx_sh_transform(fx_ctx* ctx, const float* cube, uint32_t n, float* out27);
