@@ -7,6 +7,7 @@
 //        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; the demo does not draw the ball itself)
 //        [-openWalls BITS]     (faces through which the smoke leaves, fx_set_open_walls: 1 x-, 2 x+, 4 y-, 8 y+ (up), 16 z-, 32 z+; accepts 0x.. too)
 //        [-advection maccormack|semi-lagrangian]     (the advection scheme, fx_set_advection_scheme; default: the reference's semi-Lagrangian step)
+//        [-multigrid]     (the pressure solve as two multigrid V(2,2) cycles instead of the Jacobi sweeps, fx_set_pressure_solver)
 //        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
@@ -103,6 +104,7 @@ int main(int argc, char** argv)
 	float obstacle[4] = {};
 	uint32_t openWalls = 0;                             // not in the reference: its box is closed on all six faces
 	uint32_t advection = FX_ADVECT_SEMI_LAGRANGIAN;     // not in the reference: its advection is semi-Lagrangian
+	bool multigrid = false;                             // not in the reference: its pressure solve is Jacobi sweeps
 	bool lightSet = false, pointLight = false, colorSet = false, ambientSet = false;   // not in the reference: its light is three constants (Fluid.cpp:169-173)
 	float lightPos[3] = { 75.0f, 75.0f, -75.0f }, lightColor[4] = {}, ambient[4] = {};
 	for (int i = 1; i < argc; ++i) {
@@ -131,6 +133,7 @@ int main(int argc, char** argv)
 			else if (!std::strcmp(v, "semi-lagrangian")) advection = FX_ADVECT_SEMI_LAGRANGIAN;
 			else { std::fprintf(stderr, "-advection %s: maccormack or semi-lagrangian\n", v); return 1; }
 		}
+		else if (!std::strcmp(argv[i], "-multigrid")) multigrid = true;
 		else if (!std::strcmp(argv[i], "-light") && i + 3 < argc) { for (float& v : lightPos) v = (float)atof(argv[++i]); lightSet = true; }
 		else if (!std::strcmp(argv[i], "-pointLight")) { pointLight = true; lightSet = true; }
 		else if (!std::strcmp(argv[i], "-lightColor") && i + 4 < argc) { for (float& v : lightColor) v = (float)atof(argv[++i]); colorSet = lightSet = true; }
@@ -164,6 +167,10 @@ int main(int argc, char** argv)
 	}
 	if (openWalls && !fluid.SetOpenWalls(openWalls)) { std::fprintf(stderr, "-openWalls 0x%x: %s\n", (unsigned)openWalls, fx_error_string(fluid.LastStatus())); return 1; }
 	if (advection != FX_ADVECT_SEMI_LAGRANGIAN && !fluid.SetAdvectionScheme(advection)) { std::fprintf(stderr, "-advection: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	if (multigrid) {
+		const fx_pressure_solver mg = Fluid::MultigridDefaults(grid.z > 1);
+		if (!fluid.SetPressureSolver(&mg)) { std::fprintf(stderr, "-multigrid: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	}
 	if (lightSet && grid.z <= 1) std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: a 2-D grid has no light; ignored\n");
 	if (lightSet && grid.z > 1 && !fluid.SetLight(lightPos, pointLight, colorSet ? lightColor : nullptr, ambientSet ? ambient : nullptr)) {
 		std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: %s\n", fx_error_string(fluid.LastStatus()));

@@ -30,6 +30,9 @@ MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
 WALL_X_LO, WALL_X_HI, WALL_Y_LO, WALL_Y_HI, WALL_Z_LO, WALL_Z_HI = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20   # FX_WALL_*: fx_set_open_walls
 WALL_ALL = 0x3F
 ADVECT_SEMI_LAGRANGIAN, ADVECT_MACCORMACK = 0, 1   # FX_ADVECT_*: fx_set_advection_scheme
+PRESSURE_JACOBI, PRESSURE_MULTIGRID = 0, 1         # FX_PRESSURE_*: fx_set_pressure_solver
+MG_NO_TAIL = 0x1                                   # FX_MG_NO_TAIL
+MG_MAX_LEVELS = 12                                 # FX_MG_MAX_LEVELS
 
 
 class Desc(C.Structure):
@@ -63,6 +66,11 @@ class Buoyancy(C.Structure):
 
 class HeatSource(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_float), ("rate", C.c_float)]
+
+
+class PressureSolver(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("cycles", C.c_uint32), ("pre_sweeps", C.c_uint32), ("post_sweeps", C.c_uint32),
+                ("coarse_sweeps", C.c_uint32), ("max_levels", C.c_uint32), ("omega", C.c_float)]
 
 
 class Timing(C.Structure):
@@ -121,6 +129,10 @@ SYMBOLS = {
     "fx_open_inflow": (C.c_int, [_vp, _vp]),
     "fx_set_advection_scheme": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_advection_scheme": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "fx_set_pressure_solver": (C.c_int, [_vp, C.POINTER(PressureSolver)]),
+    "fx_get_pressure_solver": (C.c_int, [_vp, C.POINTER(PressureSolver)]),
+    "fx_pressure_solve": (C.c_int, [_vp, _vp]),
+    "fx_download_pressure_level": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, C.c_size_t]),
     "fx_sh_transform": (C.c_int, [_vp, _fp, C.c_uint32, _fp]),
     "fx_set_environment": (C.c_int, [_vp, _fp, C.c_uint32]),
     "fx_render_environment": (C.c_int, [_vp, _vp, C.c_uint8]),

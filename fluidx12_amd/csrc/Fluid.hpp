@@ -157,6 +157,15 @@ public:
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }
 	bool GetAdvectionScheme(uint32_t& scheme) { m_status = fx_get_advection_scheme(m_ctx, &scheme); return m_status == FX_OK; }
 
+	// not in the reference (its pressure solve is Jacobi sweeps only): the pressure solver of Simulate and PressureSolve (fx_set_pressure_solver;
+	// nullptr or kind FX_PRESSURE_JACOBI = the default, FX_PRESSURE_MULTIGRID = geometric V-cycles), the stage alone (fx_pressure_solve) and a
+	// level of the last solve (fx_download_pressure_level).  MultigridDefaults: 2 V(2,2) cycles, 16 coarse sweeps, omega 6/7 (3-D) or 4/5 (2-D)
+	static fx_pressure_solver MultigridDefaults(bool is3d) { return fx_pressure_solver{ FX_PRESSURE_MULTIGRID, 0u, 2u, 2u, 2u, 16u, 0u, is3d ? 6.0f / 7.0f : 4.0f / 5.0f }; }
+	bool SetPressureSolver(const fx_pressure_solver* solver) { m_status = fx_set_pressure_solver(m_ctx, solver); return m_status == FX_OK; }
+	bool GetPressureSolver(fx_pressure_solver& solver) { m_status = fx_get_pressure_solver(m_ctx, &solver); return m_status == FX_OK; }
+	bool PressureSolve(void* stream = nullptr) { m_status = fx_pressure_solve(m_ctx, stream); return m_status == FX_OK; }
+	bool DownloadPressureLevel(uint32_t level, int what, float* host, size_t bytes) { m_status = fx_download_pressure_level(m_ctx, level, what, host, bytes); return m_status == FX_OK; }
+
 	// not in the reference (its only lift is the constant force inside its impulse ball): buoyancy -- a temperature advected with the flow that
 	// lifts the smoke, and the smoke's weight (fx_set_buoyancy; nullptr = off, the default) --, its heat sources (fx_set_heat_sources) and the
 	// stage alone (fx_heat), beside Emit.  The field is FX_FIELD_TEMPERATURE while buoyancy is on

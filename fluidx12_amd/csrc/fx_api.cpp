@@ -478,6 +478,7 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 		ctx->obst_cells = 0;
 		return FX_OK;
 	}
+	if (ctx->solver.kind == FX_PRESSURE_MULTIGRID) return FX_E_STATE;          // the multigrid solve has no coarse code volumes
 	const size_t n = ctx->g.plane() * (size_t)ctx->g.Zg;
 	if (bytes != n) return FX_E_INVALID;
 	hipStream_t s = pick_stream(ctx, stream);
@@ -530,6 +531,7 @@ int fx_set_open_walls(fx_ctx* ctx, uint32_t faces)
 	if (const int rc = sim_guard(ctx)) return rc;
 	if (!open_faces_ok(ctx->g, faces)) return FX_E_INVALID;                 // (a 2-D grid has no z faces)
 	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no open-wall kernels
+	if (faces && ctx->solver.kind == FX_PRESSURE_MULTIGRID) return FX_E_STATE; // the multigrid solve knows closed walls only
 	ctx->open_faces = faces;
 	return FX_OK;
 }
@@ -654,6 +656,82 @@ int fx_get_advection_scheme(fx_ctx* ctx, uint32_t* scheme)
 	if (!scheme) return FX_E_INVALID;
 	if (const int rc = sim_guard(ctx, false)) return rc;                     // (slab ranks may ask: semi-Lagrangian there)
 	*scheme = ctx->adv_scheme;
+	return FX_OK;
+}
+
+// ---- the pressure solver (fx_multigrid.hip, fx_multigrid_plan.cpp) ---------------------------------------------
+static void mg_release(fx_ctx* ctx)
+{
+	if (ctx->mg_mem) (void)hipFree(ctx->mg_mem);                              // (hipFree waits for the device: nothing reads the pyramid any more)
+	ctx->mg_mem = nullptr;
+	ctx->mg = MgPlan{};
+	for (int l = 0; l < kMgMaxLevels; ++l) { ctx->mg_e[l][0] = ctx->mg_e[l][1] = ctx->mg_b[l] = nullptr; ctx->mg_cur[l] = 0; }
+}
+
+int fx_set_pressure_solver(fx_ctx* ctx, const fx_pressure_solver* solver)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (solver && solver->kind != FX_PRESSURE_JACOBI && solver->kind != FX_PRESSURE_MULTIGRID) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	if (!solver || solver->kind == FX_PRESSURE_JACOBI) {                      // the default: every launch is the plain one again, the pyramid goes
+		mg_release(ctx);
+		ctx->solver = fx_pressure_solver{ FX_PRESSURE_JACOBI, 0u, 0u, 0u, 0u, 0u, 0u, 0.0f };
+		return FX_OK;
+	}
+	const fx_pressure_solver& ps = *solver;
+	if ((ps.flags & ~(uint32_t)FX_MG_NO_TAIL) || ps.cycles < 1 || ps.cycles > 64 || ps.pre_sweeps > 64 || ps.post_sweeps > 64 ||
+		ps.coarse_sweeps < 1 || ps.coarse_sweeps > 256 || ps.max_levels > FX_MG_MAX_LEVELS || !std::isfinite(ps.omega) || !(ps.omega > 0.0f) || ps.omega > 1.0f)
+		return FX_E_INVALID;
+	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // the per-cell freeze solve has no coarse levels
+	if (ctx->obst_code || ctx->open_faces) return FX_E_STATE;               // their boundary rules have no coarse counterpart yet
+	MgPlan plan;
+	mg_plan(ctx->g, ps.max_levels, &plan);
+	// the pyramid of the new plan is built beside the one in force, which stays in force if the allocation fails
+	const size_t align = 64;                                                  // floats: every buffer starts on a 256-byte boundary
+	size_t total = 0;
+	for (int l = 1; l < plan.levels; ++l) total += 3 * ((plan.lv[l].cells() + align - 1) / align * align);
+	float* mem = nullptr;
+	if (total && hipMalloc((void**)&mem, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return FX_E_NOMEM; }
+	if (mem && hipMemset(mem, 0, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(mem); return FX_E_DEVICE; }
+	mg_release(ctx);
+	ctx->mg_mem = mem;
+	ctx->mg = plan;
+	for (int l = 1; l < plan.levels; ++l) {
+		const size_t n = (plan.lv[l].cells() + align - 1) / align * align;
+		ctx->mg_e[l][0] = mem; ctx->mg_e[l][1] = mem + n; ctx->mg_b[l] = mem + 2 * n;
+		mem += 3 * n;
+	}
+	ctx->solver = ps;
+	return FX_OK;
+}
+
+int fx_get_pressure_solver(fx_ctx* ctx, fx_pressure_solver* out)
+{
+	if (!out) return FX_E_INVALID;
+	if (const int rc = sim_guard(ctx, false)) return rc;                     // (slab ranks may ask: Jacobi there)
+	*out = ctx->solver;
+	out->max_levels = ctx->solver.kind == FX_PRESSURE_MULTIGRID ? (uint32_t)ctx->mg.levels : 1u;
+	return FX_OK;
+}
+
+int fx_pressure_solve(fx_ctx* ctx, void* stream)
+{
+	if (!ctx || ctx->nranks > 1) return FX_E_INVALID;
+	if (ctx->desc.flags & FX_FLAG_RENDER_ONLY) return FX_E_STATE;
+	std::vector<fx_ctx*> M{ ctx };
+	return pressure_solve_all(ctx, M, pick_stream(ctx, stream));
+}
+
+int fx_download_pressure_level(fx_ctx* ctx, uint32_t level, int what, void* host, size_t bytes)
+{
+	if (!host || (what != 0 && what != 1)) return FX_E_INVALID;
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (level == 0) return fx_download(ctx, what ? FX_FIELD_DIVERGENCE : FX_FIELD_PRESSURE, host, bytes);
+	if (ctx->solver.kind != FX_PRESSURE_MULTIGRID || level >= (uint32_t)ctx->mg.levels) return FX_E_INVALID;
+	if (bytes != ctx->mg.lv[level].cells() * sizeof(float)) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	FX_HIP(hipDeviceSynchronize());
+	FX_HIP(hipMemcpy(host, what ? ctx->mg_b[level] : ctx->mg_e[level][ctx->mg_cur[level]], bytes, hipMemcpyDeviceToHost));
 	return FX_OK;
 }
 

@@ -84,6 +84,15 @@ struct fx_ctx {
 	uint32_t adv_scheme = FX_ADVECT_SEMI_LAGRANGIAN;
 	float* mc_vel = nullptr;        // three planes of X * Y * Z
 	float* mc_col = nullptr;        // float4 per cell
+	// the pressure solver (fx_set_pressure_solver; configuration on the same terms): the multigrid pyramid -- per coarse level two correction
+	// buffers and a right-hand side, one allocation, made by the first switch to FX_PRESSURE_MULTIGRID and freed by the switch back
+	// (fx_multigrid.hip; level 0 is p[] and b).  mg_cur[l]: which of a coarse level's two buffers holds what the last solve left there
+	fx_pressure_solver solver = { FX_PRESSURE_JACOBI, 0u, 0u, 0u, 0u, 0u, 0u, 0.0f };
+	fx::MgPlan mg = {};
+	float* mg_mem = nullptr;
+	float* mg_e[fx::kMgMaxLevels][2] = {};
+	float* mg_b[fx::kMgMaxLevels] = {};
+	int mg_cur[fx::kMgMaxLevels] = {};
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -106,6 +106,7 @@ int enforce_phase(fx_ctx* ctx, hipStream_t s);       // the solid cells of veloc
 int confine_phase(fx_ctx* ctx, hipStream_t s);       // vorticity confinement of velocity[1]; nothing with epsilon = 0 or dt <= 0
 int divergence_phase(fx_ctx* ctx, hipStream_t s);
 int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t iters);
+int pressure_solve_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s);   // the solver stage of the step: jacobi_all(jacobi_iters), or the multigrid V-cycles (fx_set_pressure_solver)
 int project_phase(fx_ctx* ctx, hipStream_t s);
 int simulate_impl(fx_ctx* ctx, hipStream_t s);
 

@@ -109,6 +109,23 @@ hipError_t launch_heat(const Geom& g, int half_store, const fx_buoyancy& b, cons
 const int kMcTileX = 64, kMcTileY = 4;
 hipError_t launch_maccormack(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const void* col_in, void* vel_out, void* col_out,
 	float* hat_vel, float* hat_col, float* alpha_out, hipStream_t s);
+// ---- the multigrid pressure solver (fx_multigrid.hip, fx_multigrid_plan.cpp; fx_set_pressure_solver), whole grids with closed walls and no
+// obstacles only.  mg_plan (host code, no device needed): the levels of a grid under a cap (0: none) and the level the LDS tail starts at
+// (0: no tail) with the floats of LDS it takes -> the level count
+const int kMgMaxLevels = (int)FX_MG_MAX_LEVELS, kMgTailCells = 4096, kMgTailLdsBytes = 64 * 1024;
+struct MgDims { int X, Y, Z; __host__ __device__ size_t cells() const { return (size_t)X * Y * Z; } };
+struct MgPlan { int levels, tail, tail_floats; MgDims lv[kMgMaxLevels]; };
+int mg_plan(const Geom& g, unsigned max_levels, MgPlan* out);
+// one damped lock-step sweep e_in -> e_out (p' = fma(omega, J - p, p)); e_in null: the input is all +0 and is not read (the same bits)
+hipError_t launch_mg_smooth(const MgDims& d, int is3d, const float* e_in, const float* b, float* e_out, float omega, hipStream_t s);
+// the residual of (p, b) on the fine level, restricted: one value of b_coarse per 2 x 2 (x 2) fine cells; no fine-size residual is stored
+hipError_t launch_mg_residual_restrict(const MgDims& fine, int is3d, const float* p, const float* b, float* b_coarse, hipStream_t s);
+// p += the (bi-, tri-)linear prolongation of the coarse correction e, in place
+hipError_t launch_mg_prolong_correct(const MgDims& fine, int is3d, float* p, const float* e_coarse, hipStream_t s);
+// the rest of a cycle from level plan.tail down in one workgroup: reads b[plan.tail], leaves every level's correction in e[l] and the lower
+// levels' right-hand sides in b[l] (arrays indexed by level; entries below plan.tail unused)
+struct MgTailArgs { int first, levels, is3d, pre, post, coarse; float omega; MgDims lv[kMgMaxLevels]; float* e[kMgMaxLevels]; float* b[kMgMaxLevels]; };
+hipError_t launch_mg_tail(const MgTailArgs& a, int lds_floats, hipStream_t s);
 // ---- open walls (the inflow pass: fx_open.hip; the sweeps and the projection: the bnd launchers below), whole grids only (hipErrorNotSupported
 // for a slab geometry).  faces: FX_WALL_* bits, the code byte's bit order (x-, x+, y-, y+, z-, z+; no z bit on a 2-D grid: hipErrorInvalidValue)
 // The share of a linear sample at t = i0 + f (i0 = fl = floor(t), taps i0 and i0 + 1 of an axis of n cells) that lies inside the box when the

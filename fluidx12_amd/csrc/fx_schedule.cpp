@@ -708,6 +708,72 @@ int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t it
 }
 
 
+// FX_PRESSURE_MULTIGRID (a whole-grid context in fixed mode with closed walls and no obstacles: fx_set_pressure_solver refuses the others):
+// `cycles` V-cycles on the pyramid of ctx->mg, level 0 = p[] / b.  A sweep flips a level's ping-pong; the first sweep on a coarse level reads
+// no input (all +0), and with no pre-sweeps there the correction is cleared by a memset instead.  From level mg.tail down one launch runs the
+// rest of the cycle (fx_multigrid.hip: k_mg_tail) unless FX_MG_NO_TAIL asks for the launches per level.  One mark over the whole solve:
+// launches counts everything enqueued, sweeps the level-0 sweeps
+namespace {
+struct MgRun {
+	fx_ctx* ctx; hipStream_t s; ScopedMark* mk; int is3d, tail;
+	float* cur(int l) const { return l ? ctx->mg_e[l][ctx->mg_cur[l]] : ctx->p[ctx->p_cur]; }
+	float* other(int l) const { return l ? ctx->mg_e[l][ctx->mg_cur[l] ^ 1] : ctx->p[ctx->p_cur ^ 1]; }
+	float* rhs(int l) const { return l ? ctx->mg_b[l] : ctx->b; }
+	void flip(int l) const { if (l) ctx->mg_cur[l] ^= 1; else ctx->p_cur ^= 1; }
+	// `n` sweeps on level l; fresh: the level's correction is all +0 and stored nowhere yet
+	int smooth(int l, uint32_t n, bool fresh) const
+	{
+		const fx::MgDims& d = ctx->mg.lv[l];
+		for (uint32_t i = 0; i < n; ++i) {
+			FX_HIP(fx::launch_mg_smooth(d, is3d, fresh && !i ? nullptr : cur(l), rhs(l), other(l), ctx->solver.omega, s));
+			flip(l);
+			mk->launches += 1;
+			if (!l) mk->sweeps += 1;
+		}
+		if (fresh && !n) { FX_HIP(hipMemsetAsync(cur(l), 0, d.cells() * sizeof(float), s)); mk->launches += 1; }
+		return FX_OK;
+	}
+	int cycle(int l) const
+	{
+		const fx_pressure_solver& ps = ctx->solver;
+		int rc;
+		if (l == ctx->mg.levels - 1) return smooth(l, ps.coarse_sweeps, l > 0);
+		if ((rc = smooth(l, ps.pre_sweeps, l > 0))) return rc;
+		FX_HIP(fx::launch_mg_residual_restrict(ctx->mg.lv[l], is3d, cur(l), rhs(l), rhs(l + 1), s));
+		mk->launches += 1;
+		if (l + 1 == tail) {
+			fx::MgTailArgs a = {};
+			a.first = tail; a.levels = ctx->mg.levels; a.is3d = is3d;
+			a.pre = (int)ps.pre_sweeps; a.post = (int)ps.post_sweeps; a.coarse = (int)ps.coarse_sweeps; a.omega = ps.omega;
+			for (int k = tail; k < ctx->mg.levels; ++k) { a.lv[k] = ctx->mg.lv[k]; ctx->mg_cur[k] = 0; a.e[k] = ctx->mg_e[k][0]; a.b[k] = ctx->mg_b[k]; }
+			FX_HIP(fx::launch_mg_tail(a, ctx->mg.tail_floats, s));
+			mk->launches += 1;
+		} else if ((rc = cycle(l + 1))) return rc;
+		FX_HIP(fx::launch_mg_prolong_correct(ctx->mg.lv[l], is3d, cur(l), cur(l + 1), s));
+		mk->launches += 1;
+		return smooth(l, ps.post_sweeps, false);
+	}
+};
+}  // namespace
+
+static int multigrid_solve(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->mg_mem && ctx->mg.levels > 1) { ctx->last_error = "multigrid solve without its pyramid"; return FX_E_STATE; }
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_JACOBI);
+	const MgRun run{ ctx, s, &mk, ctx->g.Zg > 1 ? 1 : 0, (ctx->solver.flags & FX_MG_NO_TAIL) ? 0 : ctx->mg.tail };
+	for (uint32_t c = 0; c < ctx->solver.cycles; ++c)
+		if (const int rc = run.cycle(0)) return rc;
+	return FX_OK;
+}
+
+int pressure_solve_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s)
+{
+	if (lead->solver.kind == FX_PRESSURE_MULTIGRID) return multigrid_solve(lead, s);
+	return jacobi_all(lead, M, s, lead->desc.jacobi_iters);
+}
+
+
 int project_phase(fx_ctx* ctx, hipStream_t s)
 {
 	DeviceGuard dg(ctx->device);
@@ -753,7 +819,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		if ((rc = do_exchange(ctx, M, &uz, 1, ON_COMPUTE, s))) return rc;
 		if (takes_sparse_solver(ctx, ctx->desc.jacobi_iters) && jacobi_freeze_can_fuse_divergence(ctx->g)) ctx->fz_fuse_div = true;   // k_freeze_dense computes it
 		else for (fx_ctx* m : M) if ((rc = divergence_phase(m, CS(m, s)))) return rc;
-		rc = jacobi_all(ctx, M, s, ctx->desc.jacobi_iters);
+		rc = pressure_solve_all(ctx, M, s);
 		ctx->fz_fuse_div = false;                      // (consumed by the dense sweep; never left standing for a later stage call)
 		if (rc) return rc;
 		for (fx_ctx* m : M) if ((rc = project_phase(m, CS(m, s)))) return rc;

@@ -374,6 +374,55 @@ class Fluid:
         capi.check(self._lib.fx_get_advection_scheme(self._ctx, C.byref(scheme)), "GetAdvectionScheme")
         return int(scheme.value)
 
+    def SetPressureSolver(self, kind="multigrid", cycles=2, pre_sweeps=2, post_sweeps=2, coarse_sweeps=16, max_levels=0, omega=None, flags=0):
+        """the pressure solver of Simulate and PressureSolve (fx_set_pressure_solver): "jacobi" (the default: jacobi_iters sweeps) or "multigrid"
+        (`cycles` V(pre_sweeps, post_sweeps) cycles of damped Jacobi, coarse_sweeps on the coarsest level, at most max_levels levels, 0 = as many
+        as the grid allows), or the capi.PRESSURE_* value.  omega: the damping, default 6/7 in 3-D and 4/5 in 2-D.  flags: capi.MG_NO_TAIL.
+        Jacobi(iters) stays plain Jacobi.  Configuration: kept across UpdateFrame, not stored in checkpoints (set it again after LoadCheckpoint).
+        Whole-grid contexts in fixed mode with closed walls and no obstacles only."""
+        self._need()
+        if isinstance(kind, str):
+            names = {"jacobi": capi.PRESSURE_JACOBI, "multigrid": capi.PRESSURE_MULTIGRID}
+            if kind.lower() not in names:
+                raise ValueError("unknown pressure solver %r" % (kind,))
+            kind = names[kind.lower()]
+        if int(kind) == capi.PRESSURE_JACOBI:
+            capi.check(self._lib.fx_set_pressure_solver(self._ctx, None), "SetPressureSolver")
+            return
+        if omega is None:
+            omega = 6.0 / 7.0 if self.grid[2] > 1 else 4.0 / 5.0
+        ps = capi.PressureSolver(int(kind), int(flags), int(cycles), int(pre_sweeps), int(post_sweeps), int(coarse_sweeps), int(max_levels), float(omega))
+        capi.check(self._lib.fx_set_pressure_solver(self._ctx, C.byref(ps)), "SetPressureSolver")
+
+    def GetPressureSolver(self):
+        """the setting in force as a dict (fx_get_pressure_solver); "max_levels" holds the levels in use"""
+        self._need()
+        ps = capi.PressureSolver()
+        capi.check(self._lib.fx_get_pressure_solver(self._ctx, C.byref(ps)), "GetPressureSolver")
+        return {name: getattr(ps, name) for name, _ in capi.PressureSolver._fields_}
+
+    def PressureSolve(self, stream=None):
+        """the solver stage alone, between Divergence and Project (fx_pressure_solve): jacobi_iters Jacobi sweeps or the multigrid cycles"""
+        self._need()
+        capi.check(self._lib.fx_pressure_solve(self._ctx, stream), "PressureSolve")
+
+    def _pressure_level_shape(self, level):
+        """(Z, Y, X) of a level the solver in force has"""
+        level = int(level)
+        if not 0 <= level < self.GetPressureSolver()["max_levels"]:
+            raise ValueError("pressure level %d: the solver in force has %d" % (level, self.GetPressureSolver()["max_levels"]))
+        X, Y, Z = self.grid
+        for _ in range(level):
+            X, Y, Z = X // 2, Y // 2, (Z // 2 if self.grid[2] > 1 else 1)
+        return (Z, Y, X)
+
+    def DownloadPressureLevel(self, level, what=0):
+        """what = 0: the solution (level 0) or the correction the last solve left on `level`; 1: its right-hand side (fx_download_pressure_level)"""
+        self._need()
+        out = np.empty(self._pressure_level_shape(level), np.float32)
+        capi.check(self._lib.fx_download_pressure_level(self._ctx, int(level), int(what), out.ctypes.data_as(C.c_void_p), out.nbytes), "DownloadPressureLevel")
+        return out
+
     def SetBuoyancy(self, ambient=0.0, density_weight=0.0, lift=0.0, cooling=0.0, up=(0.0, 1.0, 0.0), flags=0):
         """buoyancy (fx_set_buoyancy): a temperature field advected with the flow, cooling towards `ambient` by max(1 - cooling * dt, 0) per step,
         and the force (-density_weight * COLOR.w + lift * (T - ambient)) * up on VELOCITY1, one pass behind the emitters.  `up` is used as given.

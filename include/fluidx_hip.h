@@ -506,6 +506,59 @@ int fx_heat(fx_ctx* ctx, void* stream);
 int fx_set_advection_scheme(fx_ctx* ctx, uint32_t scheme);
 int fx_get_advection_scheme(fx_ctx* ctx, uint32_t* scheme);
 
+/* The pressure solver (no reference counterpart: the reference's CSProject relaxes with Jacobi sweeps only).  FX_PRESSURE_JACOBI, the default,
+ * is fx_desc.jacobi_iters lock-step sweeps, every launch the one it is without this function.  FX_PRESSURE_MULTIGRID runs `cycles` geometric
+ * V-cycles of damped Jacobi on the same operator (clamped walls, sum(q) - 6 p = b; 2-D: 4 p) from the same warm start: fx_simulate and
+ * fx_pressure_solve then ignore jacobi_iters; fx_jacobi(iters) stays plain Jacobi whatever is set.
+ * Levels: level 0 is the grid; level l + 1 halves X, Y and (3-D) Z of level l, and exists only while every extent to be halved is even and
+ * >= 4 -- an odd extent is not coarsened: a half-covered last coarse cell has no consistent coarse operator here yet, and the V-cycle slowly
+ * diverges with either naive one --, below max_levels and below 12 levels.  256^3 has 8 levels (down to 2^3), 150^3 two (75^3), 37 x 37 one;
+ * with one level a solve is cycles x coarse_sweeps damped sweeps.
+ * Arithmetic, fp32, every operation rounded as written, fma only where it says so (tests/multigrid_ref.py restates it in numpy); neighbours
+ * L, R (x -+ 1), U, D (y -+ 1), F, B (z -+ 1) by clamped index:
+ *   sweep      J = ((((((L - b) + R) + U) + D) + F) + B) * (1/6 as 0x3e2aaaab)    2-D: ((((L - b) + R) + U) + D) * 0.25
+ *              p' = fma(omega, J - p, p)            lock step, out of place: the pressure ping-pong flips as in the Jacobi solve
+ *   residual   S = (((((L + R) + U) + D) + F) + B)      r = fma(6, p, b - S)      2-D: four neighbours and 4
+ *   restrict   b_c = 0.5 * (((r000 + r100) + (r010 + r110)) + ((r001 + r101) + (r011 + r111)))  (index order x, y, z)
+ *              2-D: b_c = (r00 + r10) + (r01 + r11).  The coarse operator is the same unscaled stencil (hence 4 x the mean); the coarse
+ *              correction starts at +0
+ *   prolong    per axis, fine index i: parent j = i >> 1, other o = clamp(j + (i odd ? 1 : -1), 0, n_c - 1), v = fma(0.25, e[o] - e[j], e[j]);
+ *              x, then y, then z (3-D); p += v, in place on the current buffer
+ *   cycle(l)   last level: coarse_sweeps sweeps.  Otherwise pre_sweeps sweeps; restrict the residual into level l + 1; cycle(l + 1) from +0;
+ *              prolong and correct; post_sweeps sweeps
+ * From the first level >= 1 with at most 4096 cells down, the rest of the cycle runs as one launch of one workgroup in the LDS (the "tail":
+ * those levels are bound by launch latency); FX_MG_NO_TAIL runs them as launches of their own instead -- the same bits, a diagnostic.
+ * fx_set_pressure_solver: NULL or kind FX_PRESSURE_JACOBI returns to the default and frees the pyramid (per coarse level two correction buffers
+ * and a right-hand side, about 1.7 bytes per fine cell in all), which the first switch to multigrid allocates: FX_E_NOMEM if that fails, the
+ * state as it was.  Configuration like the emitters: per context, kept across fx_update_frame, not checkpointed (the pressure itself is: a
+ * resumed run that sets the solver again continues bit for bit), not part of fx_field_digest.
+ * FX_E_INVALID: a NULL ctx or out-pointer, an unknown kind or flag, cycles outside 1..64, pre_sweeps / post_sweeps above 64, coarse_sweeps
+ * outside 1..256, max_levels above 12, omega not finite or outside (0, 1], slab ranks, FX_JACOBI_FAITHFUL contexts.  FX_E_STATE:
+ * FX_FLAG_RENDER_ONLY contexts; multigrid requested while obstacles or an open wall are set, and fx_set_obstacles (non-NULL) /
+ * fx_set_open_walls (non-zero) while multigrid is set -- their boundary rules have no coarse counterpart yet.
+ * fx_get_pressure_solver: the setting in force; max_levels = the levels in use (1 under FX_PRESSURE_JACOBI; the other fields are then 0).
+ * fx_pressure_solve: the stage fx_simulate runs between fx_divergence and fx_project, under either kind.
+ * fx_download_pressure_level: what = 0 the solution (level 0: FX_FIELD_PRESSURE) or the correction the last solve left on a level >= 1,
+ * what = 1 the right-hand side (level 0: FX_FIELD_DIVERGENCE); float[Z_l][Y_l][X_l], bytes exact; FX_E_INVALID for a level not in use.
+ * Timing: booked under the Jacobi mark; `launches` counts every launch of a solve, `sweeps` the level-0 smoothing sweeps. */
+#define FX_PRESSURE_JACOBI    0u   /* default: fx_desc.jacobi_iters sweeps, every launch the one it is without fx_set_pressure_solver */
+#define FX_PRESSURE_MULTIGRID 1u
+#define FX_MG_NO_TAIL         0x1u /* diagnostic: every level runs as launches of its own */
+#define FX_MG_MAX_LEVELS      12u
+typedef struct fx_pressure_solver {      /* 32 bytes */
+	uint32_t kind, flags;
+	uint32_t cycles;         /* V-cycles per solve, 1..64 */
+	uint32_t pre_sweeps;     /* 0..64 */
+	uint32_t post_sweeps;    /* 0..64 */
+	uint32_t coarse_sweeps;  /* sweeps on the coarsest level, 1..256 */
+	uint32_t max_levels;     /* set: cap, 0 = as many as the grid allows; get: the levels in use */
+	float    omega;          /* damping, finite, 0 < omega <= 1 */
+} fx_pressure_solver;
+int fx_set_pressure_solver(fx_ctx* ctx, const fx_pressure_solver* solver);
+int fx_get_pressure_solver(fx_ctx* ctx, fx_pressure_solver* out);
+int fx_pressure_solve(fx_ctx* ctx, void* stream);
+int fx_download_pressure_level(fx_ctx* ctx, uint32_t level, int what, void* host, size_t bytes);
+
 /* LightProbe::TransformSH + GetSH (LightProbe.h:22,26; LightProbeEZ.cpp:117-123,183-278):
  * order-3 SH of a radiance cube float[6][N][N][3] (host), coefficients to out27 (host) */
 int fx_sh_transform(fx_ctx* ctx, const float* cube, uint32_t n, float* out27);
