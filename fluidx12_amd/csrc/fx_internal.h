@@ -30,8 +30,10 @@ struct Geom {
 inline bool whole_grid(const Geom& g) { return g.nz == g.Zg && g.H == 0; }
 // faces holds FX_WALL_* bits only, and no z face on a 2-D grid
 inline bool open_faces_ok(const Geom& g, unsigned faces) { return !(faces & ~0x3Fu) && !(g.Zg <= 1 && (faces & (FX_WALL_Z_LO | FX_WALL_Z_HI))); }
-// the colour field, the largest one, takes 4 GiB or more in fp32: the kernels that address by byte offset need 64-bit ones (WIDE, fx_store.h)
-inline bool colour_wants_wide_offsets(const Geom& g) { return g.cells_local() * 16 >= ((size_t)1 << 32); }
+// the colour field, the largest one, takes 4 GiB or more in fp32: the kernels that address by byte offset need 64-bit ones (WIDE, fx_store.h).
+// WIDE_OFFSETS = 1 (lab builds): on every grid, so that tests/test_gpu_store_edges.py can run the WIDE instantiations at all
+inline bool lab_wide_offsets() { return FX_KNOB_INT("WIDE_OFFSETS", 0) != 0; }
+inline bool colour_wants_wide_offsets(const Geom& g) { return g.cells_local() * 16 >= ((size_t)1 << 32) || lab_wide_offsets(); }
 
 // frame constants of the ray-march kernels (Common.hlsli:15-30 cbPerObject/cbPerFrame)
 struct FrameConsts {

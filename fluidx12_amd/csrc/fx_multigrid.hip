@@ -369,7 +369,7 @@ __global__ __launch_bounds__(MG_TAIL_THREADS) void k_mg_tail(const MgTailArgs a)
 // launchers
 // ---------------------------------------------------------------------------------------------
 static bool mg_dims_ok(const MgDims& d, int is3d) { return d.X > 0 && d.Y > 0 && d.Z > 0 && (is3d || d.Z == 1); }
-static bool mg_wide(const MgDims& d) { return d.cells() * 4 >= ((size_t)1 << 32); }
+static bool mg_wide(const MgDims& d) { return d.cells() * 4 >= ((size_t)1 << 32) || lab_wide_offsets(); }      // (WIDE_OFFSETS: fx_internal.h)
 static bool mg_halves(const MgDims& d, int is3d) { return !(d.X & 1) && !(d.Y & 1) && (!is3d || !(d.Z & 1)); }
 
 hipError_t launch_mg_smooth(const MgDims& d, int is3d, const float* e_in, const float* b, float* e_out, float omega, hipStream_t s)

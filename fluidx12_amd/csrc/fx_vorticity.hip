@@ -156,6 +156,10 @@ __global__ __launch_bounds__(256) void k_vorticity(const Geom g, const typename 
 			const float gy = 0.5f * (sm[sc][yd + xc] - sm[sc][yu + xc]);
 			float gz = 0.0f;
 			if constexpr (IS3D) gz = 0.5f * (sm[min(k + 1, Z - 1) % 3][yc + xc] - sm[(max(k, 1) - 1) % 3][yc + xc]);
+			// 2-D: the +0 stays a register value.  As a constant it leaves Fy = +0 - gx * wz, which the backend folds into the multiply as
+			// -(gx * wz) * s: -0 where gx * wz is +0 and the expression as written gives +0 (a -0 velocity then stays -0 instead of
+			// becoming +0; tests/test_gpu_store_edges.py found it)
+			else asm("" : "+v"(gz));
 			const float l = sqrtf((gx * gx + gy * gy) + gz * gz);
 			const float s = ed / (l + 1e-6f);
 			const Vec3 w = w_cur[r], u = u_cur[r];

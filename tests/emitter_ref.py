@@ -60,9 +60,11 @@ def support(dims, e):
         return basis64(dims, e).astype(f32) >= THRESHOLD
 
 
-def apply(vel, col, emitters, dt, half=False):
+def apply(vel, col, emitters, dt, half=False, basis_scale=1.0):
     """the pass: (velocity, colour, mask of the cells inside at least one support).  half: the fields are fp16-stored -- vel / col must hold
-    fp16-representable values; every changed cell is rounded once (RNE) behind the last emitter"""
+    fp16-representable values; every changed cell is rounded once (RNE) behind the last emitter.  basis_scale: every basis times this factor
+    before it is rounded to float32 -- a stand-in for another exp2's last bits (tests/store_edges.py shows with it that a case does not
+    depend on them)"""
     _, Z, Y, X = vel.shape
     dims = (X, Y, Z)
     dt = f32(dt)
@@ -72,7 +74,7 @@ def apply(vel, col, emitters, dt, half=False):
     for e in emitters:
         ex, dx, dz = exponent(dims, e)
         with np.errstate(over="ignore", invalid="ignore"):
-            basis = np.exp2(ex.astype(f64)).astype(f32)
+            basis = (np.exp2(ex.astype(f64)) * f64(basis_scale)).astype(f32)
             m = basis >= THRESHOLD
         if not m.any():
             continue
