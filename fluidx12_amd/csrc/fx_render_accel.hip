@@ -13,6 +13,12 @@
 //     list of their z plane (one counter per plane, a cache line apart: a single list head serialises at ~90 atomics per us,
 //     which alone cost 170 us); k_light_march runs full waves over the lists, chunks of 64 voxels dealt out round-robin.
 //
+// The skip rule, for every value a field can hold (tests/test_gpu_render_edges.py): a gather is skipped only where its result is known.
+// A light / AO / gradient sample is skipped where every alpha of its block's footprint is +0 or -0 -- its trilinear value is then +0 --,
+// a view sample where every alpha of the footprint is a number of magnitude <= 0.01 -- its value cannot pass `> 0.01`.  A NaN alpha
+// makes its block occupied and visible, a negative alpha counts with its magnitude, +inf, alpha above 1 and subnormals count as what
+// they are (fold_alpha below): the plain kernels gather those samples, so these do.
+//
 // Scratch (RenderAccel, owned by the context): alpha volume, fine occupancy grid, the masks, the voxel list.
 #include "fx_march.h"
 #include <algorithm>
@@ -73,13 +79,30 @@ static const uint32_t* mask_pos(const RenderAccel& a) { return a.msh ? a.bits + 
 static const uint32_t* mask_vis(const RenderAccel& a) { return a.msh ? a.bits + 2 * (size_t)a.fine_words + a.mask_words : a.bits + a.fine_words; }
 
 // ---- acceleration structures ----------------------------------------------------------------------------------------------
-// occupancy grid: entry c bounds the alpha of the voxels [4c, 4c + 4] per axis -- everything a trilinear sample whose base tap
-// lies in block c can touch.  k_occupancy_blocks reads every alpha once, coalesced along x (lane = x, each thread folds a
+// occupancy grid: entry c bounds the |alpha| of the voxels [4c, 4c + 4] per axis (+inf where one of them is NaN: fold_alpha) -- everything
+// a trilinear sample whose base tap lies in block c can touch.  k_occupancy_blocks reads every alpha once, coalesced along x (lane = x, each thread folds a
 // 1 x 4 x 4 column, four lanes fold into one 4^3 block: no atomics) and writes it to the alpha side volume on the way;
 // k_occupancy_dilate takes the max over the 2 x 2 x 2 blocks c .. c + 1 (a superset of [4c, 4c + 4]: conservative, which only
 // skips less) and stores the two masks of the fine level by wave ballot.
 // FROM_ALPHA: the side volume holds this colour field's alpha already (the advection that made the field wrote it, fx_advect_lds.hip
 // <ALPHA>): 4 bytes per voxel to read instead of the texel, nothing to write but the block maxima.
+// What an entry is folded from: |alpha|, with NaN as +inf.  The marches ask an entry two things -- `== 0` (every sample of the block is +0:
+// nothing to gather) and `<= 0.01` (no sample passes the view march's threshold) --, and a field holds more than [0, 1]: an emitter adds
+// colour without a clamp, fp16 storage turns that into +inf, the advection's filter turns inf - inf into NaN, fx_upload takes anything.  A
+// maximum of the alphas themselves loses exactly the values that matter: fmaxf drops a NaN operand and max(0, a) drops every negative
+// alpha, whose samples the plain kernels do gather (a negative density RAISES a shadow ray's transmittance, a NaN ends up in the light
+// map).  |a| is conservative (it only skips less), -0 folds to +0 (a sample of zeros of either sign is +0), and as unsigned integers the
+// bit patterns of |a| order like the magnitudes with every NaN above +inf: one v_and and one v_max_u32 per alpha, NaN -> +inf once at the
+// store; +inf then survives every fmaxf behind (k_occupancy_dilate) and answers both questions "gather".  The alpha side volume keeps the
+// values as they are: the taps read it.
+__device__ __forceinline__ uint32_t fold_alpha(uint32_t m, float a) { return max(m, __float_as_uint(a) & 0x7FFFFFFFu); }
+__device__ __forceinline__ float folded(uint32_t m) { return __uint_as_float(min(m, 0x7F800000u)); }
+// "A sample whose filter weights are all 0 IS its base tap" (the light pass's shortcuts on grids whose voxel centres come out exact) rests on
+// fma(0, b - a, a) = a, which holds while b - a is finite: a tap that is NaN or +-inf -- or two so large that their difference overflows --
+// makes the plain kernels' sample NaN (0 * inf).  An entry of the dilated grid bounds |alpha| over everything such a sample touches: at
+// or below this (2^127 > 1e38: no difference of two overflows) the shortcut is the sample, above it the sample is taken tap by tap.
+static constexpr float kFiniteAlpha = 1.0e38f;
+
 template <bool HALF, bool FROM_ALPHA>
 __global__ __launch_bounds__(256) void k_occupancy_blocks(const Geom g, const typename ColTex<HALF>::T* __restrict__ col, float* __restrict__ blk,
 	float* __restrict__ alpha, uint32_t* __restrict__ cnt, uint32_t* __restrict__ cnt_next)
@@ -95,7 +118,7 @@ __global__ __launch_bounds__(256) void k_occupancy_blocks(const Geom g, const ty
 	const int x = blockIdx.x * 64 + (threadIdx.x & 63);
 	const int cy = blockIdx.y * 4 + (threadIdx.x >> 6), cz = blockIdx.z;
 	auto fetch = [&](size_t i) -> float { return FROM_ALPHA ? alpha[i] : ColTex<HALF>::ldw(col, i); };
-	float m = 0.0f;
+	uint32_t m = 0u;
 	if (x < g.X && cy < CY) {
 		if (4 * cz + 4 <= g.Zg && 4 * cy + 4 <= g.Y) {                             // the whole column: 16 independent loads in flight
 			float a[16];
@@ -104,7 +127,7 @@ __global__ __launch_bounds__(256) void k_occupancy_blocks(const Geom g, const ty
 #pragma unroll
 			for (int k = 0; k < 16; ++k) {
 				if (!FROM_ALPHA) alpha[((size_t)(4 * cz + (k >> 2)) * g.Y + (4 * cy + (k & 3))) * g.X + x] = a[k];
-				m = fmaxf(m, a[k]);
+				m = fold_alpha(m, a[k]);
 			}
 		} else {
 			for (int z = 4 * cz; z < min(4 * cz + 4, g.Zg); ++z)
@@ -112,13 +135,13 @@ __global__ __launch_bounds__(256) void k_occupancy_blocks(const Geom g, const ty
 					const size_t i = ((size_t)z * g.Y + y) * g.X + x;
 					const float a = fetch(i);
 					if (!FROM_ALPHA) alpha[i] = a;
-					m = fmaxf(m, a);
+					m = fold_alpha(m, a);
 				}
 		}
 	}
-	m = fmaxf(m, __shfl_xor(m, 1));
-	m = fmaxf(m, __shfl_xor(m, 2));
-	if (x < g.X && cy < CY && (x & 3) == 0) blk[((size_t)cz * CY + cy) * CX + (x >> 2)] = m;
+	m = max(m, (uint32_t)__shfl_xor((int)m, 1));
+	m = max(m, (uint32_t)__shfl_xor((int)m, 2));
+	if (x < g.X && cy < CY && (x & 3) == 0) blk[((size_t)cz * CY + cy) * CX + (x >> 2)] = folded(m);
 }
 
 // the same from the side volume for rows of whole quads: a lane folds a whole 4^3 block from 16 float4s
@@ -143,10 +166,10 @@ __global__ __launch_bounds__(256) void k_occupancy_blocks_a4(const Geom g, float
 		const int dz = min(k >> 2, nz - 1), dy = min(k & 3, ny - 1);             // (short blocks at the far faces fold a voxel twice)
 		a[k] = *reinterpret_cast<const float4*>(alpha + ((size_t)(4 * cz + dz) * g.Y + (4 * cy + dy)) * g.X + 4 * cx);
 	}
-	float m = 0.0f;
+	uint32_t m = 0u;
 #pragma unroll
-	for (int k = 0; k < 16; ++k) m = fmaxf(m, fmaxf(fmaxf(a[k].x, a[k].y), fmaxf(a[k].z, a[k].w)));
-	blk[((size_t)cz * CY + cy) * CX + cx] = m;
+	for (int k = 0; k < 16; ++k) m = fold_alpha(fold_alpha(fold_alpha(fold_alpha(m, a[k].x), a[k].y), a[k].z), a[k].w);
+	blk[((size_t)cz * CY + cy) * CX + cx] = folded(m);
 }
 
 // Build pass and light-map fill in one sweep over the side volume (grids whose extents are powers of two: a voxel's centre sample --
@@ -173,14 +196,14 @@ __global__ __launch_bounds__(256) void k_build_fill(const Geom g, float* __restr
 	if (valid) {
 #pragma unroll
 		for (int k = 0; k < 16; ++k) a[k] = *reinterpret_cast<const float4*>(alpha + (uint32_t)(4 * cz + (k >> 2)) * XY + (uint32_t)(4 * cy + (k & 3)) * X + 4u * (uint32_t)cx);
-		float m = 0.0f;
+		uint32_t m = 0u;
 #pragma unroll
 		for (int k = 0; k < 16; ++k) {
-			m = fmaxf(m, fmaxf(fmaxf(a[k].x, a[k].y), fmaxf(a[k].z, a[k].w)));
+			m = fold_alpha(fold_alpha(fold_alpha(fold_alpha(m, a[k].x), a[k].y), a[k].z), a[k].w);
 			const uint32_t b4 = (a[k].x >= 0.00999999978f ? 1u : 0u) | (a[k].y >= 0.00999999978f ? 2u : 0u) | (a[k].z >= 0.00999999978f ? 4u : 0u) | (a[k].w >= 0.00999999978f ? 8u : 0u);
 			lit[k >> 2] |= b4 << (4 * (k & 3));
 		}
-		blk[((size_t)cz * CY + cy) * CX + cx] = m;
+		blk[((size_t)cz * CY + cy) * CX + cx] = folded(m);
 	}
 	// The unlit value over the whole cell.  Frame after frame that value is the same and only the ray kernels write anything else, into
 	// lit voxels: a cell without a lit voxel last time still holds it everywhere.  So each pass leaves a bit per cell "holds a lit voxel"
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(256) void k_occupancy_dilate(int CX, int CY, int CZ
 		}
 		occ[c] = m;
 	}
-	// the same comparisons the marches would make on occ[c] (fx_march.h): NaN counts as occupied
+	// the same comparisons the marches would make on occ[c] (fx_march.h); an entry is never NaN -- a NaN alpha is folded as +inf: occupied and visible
 	const unsigned long long bp = __ballot(valid && !(m == 0.0f)), bv = __ballot(valid && !(m <= 0.00999999978f));
 	if ((threadIdx.x & 63) == 0 && (uint32_t)(c >> 6) < words64) { pos64[c >> 6] = bp; vis64[c >> 6] = bv; }
 }
@@ -335,7 +358,7 @@ __global__ __launch_bounds__(256) void k_light_cells(const Geom g, int CX, int C
 			for (int dy = max(cy - 1, 0); dy <= min(cy + 1, CY - 1); ++dy)
 				for (int dx = max(cx - 1, 0); dx <= min(cx + 1, CX - 1); ++dx) {
 					const float v = blk[((size_t)dz * CY + dy) * CX + dx];
-					m = v == 0.0f ? m : 1.0f;                                      // (NaN counts as occupied)
+					m = v == 0.0f ? m : 1.0f;                                      // (a NaN or negative alpha left +inf or |alpha| here: occupied)
 				}
 		occupied = m != 0.0f;
 		if (!occupied) {
@@ -400,7 +423,7 @@ __device__ __forceinline__ uint32_t find_segment(const uint32_t* pre, uint32_t n
 	return lo;
 }
 
-__global__ __launch_bounds__(256) void k_light_classify(const Geom g, const float* __restrict__ alpha, const uint32_t* __restrict__ pos_fine, int CX, int CY, int CZ,
+__global__ __launch_bounds__(256) void k_light_classify(const Geom g, const float* __restrict__ alpha, const float* __restrict__ occ, const uint32_t* __restrict__ pos_fine, int CX, int CY, int CZ,
 	const uint32_t* __restrict__ cells, uint32_t* __restrict__ list, uint32_t* __restrict__ cnt, uint32_t* __restrict__ lightmap, const FrameConsts fc, int has_sh)
 {
 	extern __shared__ uint32_t lds[];
@@ -431,7 +454,8 @@ __global__ __launch_bounds__(256) void k_light_classify(const Geom g, const floa
 			exact = bc.fx == 0.0f && bc.fy == 0.0f && bc.fz == 0.0f;
 			centre = mad24(mad24((uint32_t)bc.z0, (uint32_t)g.Y, (uint32_t)bc.y0), (uint32_t)g.X, (uint32_t)bc.x0);
 		}
-		const bool all_exact = __ballot(valid && !exact) == 0;
+		// (occ[c] covers the taps [v, v + 1] of every voxel v of cell c; uniform over the wave)
+		const bool all_exact = __ballot(valid && !exact) == 0 && occ[c] <= kFiniteAlpha;
 		if (valid) {
 			float density;
 			if (all_exact) density = alpha[centre]; else density = density_at(vol, g, pu, pv, pw);
@@ -611,7 +635,7 @@ __global__ __launch_bounds__(1024) void k_light_rays(const Geom g, const float* 
 
 // GetDensityGradient (RayMarch.hlsli:73-95) of every listed voxel: the occlusion ray's direction before normalisation -- minus the
 // gradient, or the voxel's position where the gradient vanishes (CSRayMarchL.hlsl:61-64) -- to gi[flat index][3]
-__global__ __launch_bounds__(256) void k_light_gi_dirs(const Geom g, const float* __restrict__ alpha, int CX, int CY,
+__global__ __launch_bounds__(256) void k_light_gi_dirs(const Geom g, const float* __restrict__ alpha, const float* __restrict__ occ, int CX, int CY,
 	const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, float* __restrict__ gi, unsigned long long* __restrict__ counters)
 {
 	extern __shared__ uint32_t lds[];
@@ -633,10 +657,12 @@ __global__ __launch_bounds__(256) void k_light_gi_dirs(const Geom g, const float
 		ns += 6;
 		float qxm, qxp, qym, qyp, qzm, qzp;
 		const Base c = make_base(g, u, v, w);
-		if (__builtin_amdgcn_ballot_w64(c.fx != 0.0f || c.fy != 0.0f || c.fz != 0.0f) == 0) {
+		// (the six samples touch the voxels [v - 1, v + 2] per axis: inside what the dilated entry of v - 1's cell bounds)
+		const float bound = occ[mad24(mad24((uint32_t)max((int)z - 1, 0) >> 2, (uint32_t)CY, (uint32_t)max((int)y - 1, 0) >> 2), (uint32_t)CX, (uint32_t)max((int)x - 1, 0) >> 2)];
+		if (__builtin_amdgcn_ballot_w64(c.fx != 0.0f || c.fy != 0.0f || c.fz != 0.0f || !(bound <= kFiniteAlpha)) == 0) {
 			// The six samples sit at the voxel's own centre, shifted by whole texels: where the centre's texel coordinate comes out exact
 			// (extents that are powers of two: (x + 0.5) / X * X - 0.5 = x) all three filter weights are 0 and every lerp returns its first
-			// operand, fma(0, b - a, a) = a for the finite alphas of a saturated field -- the sample IS its base tap: 6 loads, not 48.
+			// operand, fma(0, b - a, a) = a for finite alphas (kFiniteAlpha) -- the sample IS its base tap: 6 loads, not 48.
 			const uint32_t X = (uint32_t)g.X, XY = X * (uint32_t)g.Y;
 			auto tap = [&](int ox_, int oy_, int oz_) -> float {
 				const int x0 = min(max(c.ix + ox_, 0), g.X - 1), y0 = min(max(c.iy + oy_, 0), g.Y - 1), z0 = min(max(c.iz + oz_, 0), g.Zg - 1);
@@ -656,17 +682,48 @@ __global__ __launch_bounds__(256) void k_light_gi_dirs(const Geom g, const float
 	flush_counts(counters, 0u, ns, 0u);
 }
 
+// k_build_fill takes a voxel's own alpha for its centre sample, which it is while the sample's taps are finite (kFiniteAlpha).  Where they
+// are not, the plain kernels' sample is NaN and the voxel unlit.  Such cells are rare and known behind the dilation, so this pass runs
+// behind the ray kernels: it takes the real centre sample of the voxels k_build_fill listed in those cells and puts the unlit value back
+// where it is not lit (the ray cast for it was wasted; a voxel k_build_fill did not list has a sample of its own alpha or NaN: unlit too).
+__global__ __launch_bounds__(256) void k_light_fill_repair(const Geom g, int CX, int CY, int CZ, const float* __restrict__ occ, const float* __restrict__ alpha,
+	uint32_t* __restrict__ lightmap, const FrameConsts fc, int has_sh)
+{
+	const int c = blockIdx.x * 256 + threadIdx.x;
+	if (c >= CX * CY * CZ || occ[c] <= kFiniteAlpha) return;
+	const int cx = c % CX, cy = (c / CX) % CY, cz = c / (CX * CY);
+	const AccelVol<false, false> vol{ nullptr, alpha, nullptr, nullptr, nullptr, 0, CX, CY, CX, CY };
+	const float irr[3] = { 0.0f, 0.0f, 0.0f };
+	const uint32_t e = light_value(fc, has_sh != 0, 1.0f, 1.0f, irr);
+	for (int z = 4 * cz; z < min(4 * cz + 4, g.Zg); ++z)
+		for (int y = 4 * cy; y < min(4 * cy + 4, g.Y); ++y)
+			for (int x = 4 * cx; x < min(4 * cx + 4, g.X); ++x) {
+				const size_t id = ((size_t)z * g.Y + y) * g.X + x;
+				if (!(alpha[id] >= 0.00999999978f)) continue;
+				const float ox = fmaf(((float)x + 0.5f) / (float)g.X, 2.0f, -1.0f);    // CSRayMarchL.hlsl:22
+				const float oy = fmaf(((float)y + 0.5f) / (float)g.Y, 2.0f, -1.0f);
+				const float oz = fmaf(((float)z + 0.5f) / (float)g.Zg, 2.0f, -1.0f);
+				const float d = vol.density(make_taps(g, make_base(g, fmaf(ox, 0.5f, 0.5f), fmaf(oy, 0.5f, 0.5f), fmaf(oz, 0.5f, 0.5f))));   // :36-37
+				if (!(d >= 0.00999999978f)) lightmap[id] = e;                          // :44
+			}
+}
+
 hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lightmap, const FrameConsts& fc, const float* sh,
 	uint32_t num_samples, hipStream_t s, unsigned long long* counters, bool filled, int point_light)
 {
 	const int ncell = a.CX * a.CY * a.CZ;
 	uint32_t* ctr = ctr_now(a, g);
+	// (behind every return below that follows a filling build pass)
+	auto repaired = [&]() -> hipError_t {
+		if (filled) hipLaunchKernelGGL(k_light_fill_repair, dim3((ncell + 255) / 256), dim3(256), 0, s, g, a.CX, a.CY, a.CZ, a.occ, a.alpha, lightmap, fc, sh ? 1 : 0);
+		return hipGetLastError();
+	};
 	if (!filled) {                                                                 // (else k_build_fill has written the constants and the lists)
 	hipLaunchKernelGGL(k_light_cells, dim3((ncell + 255) / 256), dim3(256), 0, s, g, a.CX, a.CY, a.CZ, a.occ + ncell, a.cells, ctr, lightmap, fc, sh ? 1 : 0);
 	// (2048 persistent workgroups: 30 us at 256^3 / frame 132; 8192 -- a wave per listed cell -- 37 us.  Of today's 25.6 us: 4 the
 	// prologue, 12.5 list entry + alpha + arithmetic, 2.4 the stores, 6.6 the list atomics -- measured by leaving each out; two cells in
 	// flight per wave changed nothing: more than half of the 262 k cells of frame 132 are listed, the pass moves ~75 MB)
-	hipLaunchKernelGGL(k_light_classify, dim3((unsigned)std::min(ncell / 4 + 1, 2048)), dim3(256), ((size_t)a.CZ + 1) * 4, s, g, a.alpha, a.bits, a.CX, a.CY, a.CZ,
+	hipLaunchKernelGGL(k_light_classify, dim3((unsigned)std::min(ncell / 4 + 1, 2048)), dim3(256), ((size_t)a.CZ + 1) * 4, s, g, a.alpha, a.occ, a.bits, a.CX, a.CY, a.CZ,
 		a.cells, a.list, ctr, lightmap, fc, sh ? 1 : 0);
 	}
 	const size_t cells = (size_t)g.X * g.Y * g.Zg;
@@ -681,14 +738,14 @@ hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lig
 #define FX_SHADOW(C, M) do { if (point_light) FX_RAYS3(C, M, true); else FX_RAYS3(C, M, false); } while (0)
 	if (!sh) {
 		if (a.msh) FX_SHADOW(true, RAYS_SHADOW); else FX_SHADOW(false, RAYS_SHADOW);
-		return hipGetLastError();
+		return repaired();
 	}
 	if (a.gi) {
 		if (a.msh) FX_SHADOW(true, RAYS_SHADOW_KEEP); else FX_SHADOW(false, RAYS_SHADOW_KEEP);
-		hipLaunchKernelGGL(k_light_gi_dirs, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 2048)), dim3(256), ((size_t)g.Zg + 1) * 4, s, g, a.alpha, a.CX, a.CY,
+		hipLaunchKernelGGL(k_light_gi_dirs, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 2048)), dim3(256), ((size_t)g.Zg + 1) * 4, s, g, a.alpha, a.occ, a.CX, a.CY,
 			a.list, ctr, a.gi, counters);
 		if (a.msh) FX_RAYS(true, RAYS_AO); else FX_RAYS(false, RAYS_AO);
-		return hipGetLastError();
+		return repaired();
 	}
 #undef FX_SHADOW
 #undef FX_RAYS
@@ -699,7 +756,7 @@ hipError_t launch_accel_light(const Geom& g, const RenderAccel& a, uint32_t* lig
 	if (a.msh) { if (point_light) FX_MARCH(true, true); else FX_MARCH(true, false); }
 	else { if (point_light) FX_MARCH(false, true); else FX_MARCH(false, false); }
 #undef FX_MARCH
-	return hipGetLastError();
+	return repaired();
 }
 
 

@@ -22,7 +22,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fluidx12_amd.build import kernel_source_hash   # noqa: E402
 
-RENDER = ("k_build_fill", "k_occupancy_blocks", "k_occupancy_blocks_a4", "k_occupancy_dilate", "k_mask_coarsen", "k_light_cells", "k_light_classify", "k_light_rays", "k_light_gi_dirs",
+RENDER = ("k_build_fill", "k_occupancy_blocks", "k_occupancy_blocks_a4", "k_occupancy_dilate", "k_mask_coarsen", "k_light_cells", "k_light_classify", "k_light_rays", "k_light_gi_dirs", "k_light_fill_repair",
           "k_light_march", "k_view_slots", "k_view_march", "k_direct_march", "k_raymarch_light", "k_raymarch_view", "k_raycast_direct", "k_resolve_cube")
 
 
