@@ -34,7 +34,7 @@ namespace fx {
 
 namespace {
 
-constexpr int TX = 64;                            // voxels per workgroup and plane: TX x TY (TY = 8 rows, one per wave; 16 as an experiment)
+constexpr int TX = kAdvectTileX;                  // voxels per workgroup and plane: TX x TY (TY = 8 rows, one per wave; 16 as an experiment)
 constexpr int HX = TX + 2;                        // staged cells per row
 constexpr int NSLOT = 4;
 // staged cells per plane, bytes per velocity component (fp16 storage: the half sits zero-extended in a dword -- a 2-byte LDS-DMA load
@@ -478,47 +478,24 @@ hipError_t launch_advect_lds(const Geom& g, const SimParams& sp, int half_store,
 {
 	if (far_used) *far_used = false;
 	if (alpha) alpha->written = false;
-	auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
 	const int nzp = z_end - z_begin;
-	// rows per workgroup tile.  16 (one 1024-thread workgroup per CU, 1.16 x instead of 1.29 x border) measured 0.228 / 0.269 ms against
-	// 0.223 / 0.263 for 8 (256^3, states of step 25 / 110): the bytes it saves it loses to the single workgroup's barrier stalls
-	const bool p2 = pow2(g.X) && pow2(g.Y) && pow2(g.Zg);
-	const int TY = p2 && FX_KNOB_INT("ADVECT_TILE_ROWS", 8) == 16 ? 16 : 8;
-	// where it pays: from 4 M voxels per launch.  128^3 measured 0.032-0.040 ms against 0.030 for k_advect_fast, 150^3 0.049-0.053 against
-	// 0.057 for k_advect -- and inside whole steps, with the second launch for the far-tracing voxels, 0.0586 against 0.0555: too few
-	// workgroups either way
-	const size_t min_voxels = (size_t)1 << 22;
-	if (g.Zg <= 1 || g.X < TX || g.Y < TY || nzp < 12 || (!force && (size_t)g.X * g.Y * (size_t)nzp < min_voxels) ||
-		g.cells_local() * 16 >= ((size_t)1 << 32))
-		return hipErrorNotSupported;
-	const int half_on = FX_KNOB_INT("ADVECT_LDS_HALF", 1);
-	if (half_store && !half_on) return hipErrorNotSupported;
+	// every decision -- the staged path at all, the instantiation, the tiles and the chunks -- is advect_lds_plan's (fx_advect_plan.cpp)
+	AdvectLdsKnobs kn;
+	kn.tile_rows = FX_KNOB_INT("ADVECT_TILE_ROWS", 8);
+	kn.lds_half = FX_KNOB_INT("ADVECT_LDS_HALF", 1);
+	kn.defer = FX_KNOB_INT("ADVECT_DEFER", 1);
+	kn.zchunk = FX_KNOB("ADVECT_ZCHUNK");
+	const AdvectLdsPlan pl = advect_lds_plan(g, half_store, z_begin, z_end, force, far_scratch != nullptr, far_words, alpha && alpha->out, kn);
+	if (!pl.staged) return hipErrorNotSupported;
+	const bool p2 = pl.p2, defer = pl.defer;
+	const int TY = pl.tile_rows, ntx = pl.tiles_x, nty = pl.tiles_y, zchunk = pl.zchunk, nchunks = pl.nchunks;
 	auto lg = [](int v) { int k = 0; while ((1 << k) < v) ++k; return k; };
-	const int ntx = (g.X + TX - 1) / TX, nty = (g.Y + TY - 1) / TY;
 	const int lgX = lg(g.X), lgY = lg(g.Y), lg_gx = p2 ? lg(ntx) : ntx, lg_gy = p2 ? lg(nty) : nty;      // (other extents: the kernel gets the tile counts themselves)
 	const int tiles_xy = ntx * nty;
-	// planes per workgroup.  Every chunk re-reads two planes.  While the far-tracing voxels were gathered inside this kernel the
-	// workgroups over the plume took several times longer than the rest and short chunks (2048 workgroups of 16 planes at 256^3)
-	// balanced that: 0.216 ms with 16, 0.219 with 8, 0.241 with 32, 0.258 with 64.  With those voxels deferred every workgroup costs
-	// the same: 16 / 32 / 64 planes measure 0.211 / 0.203 / 0.212 ms (fp32), 0.147 / 0.143 / 0.144 (fp16), within the noise -- 32.
-	const bool want_defer = far_scratch && FX_KNOB_INT("ADVECT_DEFER", 1) != 0;
-	int zchunk = FX_KNOB_INT("ADVECT_ZCHUNK", want_defer ? 32 : 16);
-	// grids of a few million voxels (150^3: 57 tiles per plane) have too few workgroups for 32-plane chunks to fill the chip and too many
-	// with short ones for one resident round (two workgroups per CU): as many chunks as keep them all resident at once.  150^3, us per
-	// launch by planes per chunk: 6 49.8, 8 51.4, 12 51.2, 15 54.8, 19 49.0, 25 57.5, 32 67.5, 64 122 (k_advect: 57.3)
-	if (!p2 && !FX_KNOB("ADVECT_ZCHUNK")) {
-		const int chunks = std::max(1, 512 / tiles_xy);
-		zchunk = std::max(8, (nzp + chunks - 1) / chunks);
-	}
-	if (zchunk < 4) zchunk = 4;
-	if (zchunk > nzp) zchunk = nzp;
-	const int nchunks = (nzp + zchunk - 1) / zchunk;
 	const float rX = 1.0f / (float)g.X, rY = 1.0f / (float)g.Y, rZ = 1.0f / (float)g.Zg, inv_rr = sp.is3d ? 256.0f : 1024.0f;
-	// far-tracing voxels deferred to k_advect_far when the caller lent scratch: [two alternating totals][the common list: an id per voxel]
-	// [a segment of 64 * TY * zchunk ids per workgroup] (FLUIDX_ADVECT_DEFER=0: gathered inside the staged kernel, as before)
-	const uint32_t nwg = (uint32_t)(tiles_xy * nchunks), far_cap = (uint32_t)(TX * TY * zchunk);
+	// the scratch of the deferred voxels: [two alternating totals][the common list: an id per voxel][a segment of 64 * TY * zchunk ids per workgroup]
+	const uint32_t far_cap = (uint32_t)(TX * TY * zchunk);
 	const size_t flat_words = (size_t)g.X * g.Y * (size_t)nzp;
-	const bool defer = want_defer && far_words >= 2 + flat_words + (size_t)nwg * far_cap && ((uint64_t)g.Zg << (lgX + lgY)) <= ((uint64_t)1 << 32);   // (a note = x | y << lgX | z << lgP, or the voxel's index in the whole grid)
 	if (far_used) *far_used = defer;                              // (the caller alternates far_parity over the launches that did defer)
 	uint32_t* far_total = far_scratch ? far_scratch + (far_parity & 1) : nullptr;
 	uint32_t* far_total_next = far_scratch ? far_scratch + ((far_parity & 1) ^ 1) : nullptr;
@@ -531,9 +508,7 @@ hipError_t launch_advect_lds(const Geom& g, const SimParams& sp, int half_store,
 			z_begin, nzp, zchunk, nchunks, halo_overflow, rX, rY, rZ, inv_rr, lgX, lgY, lg_gx, lg_gy, far_list, far_flat, far_total, far_cap); } while (0)
 #define FX_FAR(H_, P_, A_) hipLaunchKernelGGL((k_advect_far<H_, P_, A_>), dim3(far_wgs), dim3(256), 0, s, g, sp, vel_in, col_in, vel_out, col_out, alpha_out, far_flat, far_total, far_total_next, halo_overflow, rX, rY, rZ, inv_rr, lgX, lgY)
 	const int far_wgs = 1024;                                       // 262144 threads: a developed 256^3 plume notes 250-400 thousand voxels
-	// the render's alpha side volume rides along on the default path (8-row tiles, far voxels deferred) of a context whose local planes
-	// are the whole grid (the side volume is indexed by global voxel)
-	float* alpha_out = alpha && alpha->out && defer && TY == 8 && g.nzl() == g.Zg && z_begin == 0 && z_end == g.Zg ? alpha->out : nullptr;
+	float* alpha_out = pl.alpha ? alpha->out : nullptr;           // the render's alpha side volume rides along
 	if (alpha_out) {
 		if (half_store) { if (p2) { FX_ADV(true, 8, true, true, true); FX_FAR(true, true, true); } else { FX_ADV(true, 8, true, false, true); FX_FAR(true, false, true); } }
 		else { if (p2) { FX_ADV(false, 8, true, true, true); FX_FAR(false, true, true); } else { FX_ADV(false, 8, true, false, true); FX_FAR(false, false, true); } }
@@ -553,14 +528,6 @@ hipError_t launch_advect_lds(const Geom& g, const SimParams& sp, int half_store,
 #undef FX_FAR
 #undef FX_ADV
 	return hipGetLastError();
-}
-
-// scratch words launch_advect_lds needs to defer far-tracing voxels for planes [z_begin, z_end) of `g` (0: no staged path there)
-size_t advect_far_words(const Geom& g, int nzp)
-{
-	if (g.Zg <= 1 || g.X < TX || g.Y < 16 || nzp < 12) return 0;
-	const size_t tiled = (size_t)((g.X + TX - 1) / TX * TX) * (size_t)((g.Y + 7) / 8 * 8);             // a plane as the 64 x 8 tiles cover it
-	return 2 + (size_t)g.X * g.Y * (size_t)nzp + tiled * (size_t)(nzp + 32);   // two totals, the common list, the workgroups' segments (whole chunks)
 }
 
 }  // namespace fx

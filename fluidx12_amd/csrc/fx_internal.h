@@ -79,6 +79,15 @@ hipError_t launch_advect_lds(const Geom& g, const SimParams& sp, int half_store,
 // far_scratch: advect_far_words(g, planes) words lent by the caller (its first two words ZEROED once; far_parity alternates over the launches that report *far_used) let the staged kernel
 // defer far-tracing voxels to a second, small launch
 size_t advect_far_words(const Geom& g, int nzp);
+// What launch_advect_lds decides before it launches (fx_advect_plan.cpp; host code, no device needed).  staged = false: the geometry has no
+// staged path.  Otherwise k_advect_lds<half_store, tile_rows, defer, p2, alpha> runs on tiles_x * tiles_y * nchunks workgroups, each a tile of
+// 64 x tile_rows voxels over zchunk planes (the last chunk: what is left), and with defer k_advect_far<half_store, p2, alpha> behind it.
+// AdvectLdsKnobs: the launcher's switches as it reads them per launch (zchunk: the ADVECT_ZCHUNK string, null while unset)
+const int kAdvectTileX = 64;
+struct AdvectLdsKnobs { int tile_rows = 8, lds_half = 1, defer = 1; const char* zchunk = nullptr; };
+struct AdvectLdsPlan { bool staged, p2; int tile_rows, tiles_x, tiles_y, zchunk, nchunks; bool defer, alpha; };
+AdvectLdsPlan advect_lds_plan(const Geom& g, int half_store, int z_begin, int z_end, bool force, bool has_scratch, size_t far_words, bool alpha_offered,
+	const AdvectLdsKnobs& k);
 // vorticity confinement of a whole-grid velocity (fx_vorticity.hip), vel_in -> vel_out (never in place: the cell stencil has radius 2);
 // hipErrorNotSupported for a slab geometry
 hipError_t launch_confine_vorticity(const Geom& g, int half_store, const void* vel_in, void* vel_out, float eps, float dt, hipStream_t s);

@@ -1,8 +1,7 @@
 """numpy model of the buoyancy pass (include/fluidx_hip.h fx_set_buoyancy, fluidx12_amd/csrc/fx_heat.hip: k_heat).
 
-The pass in fp32, operation by operation (rules 1-6 of the header comment), with the two liberties of tests/emitter_ref.py: the basis of a heat
-source is evaluated in float64 and rounded once, and a fused multiply-add is the float64 product (exact for two float32 factors) plus the
-float64 addend, rounded to float64 and then to float32.  So the tests compare
+The pass in fp32, operation by operation (rules 1-6 of the header comment), with the liberty of tests/emitter_ref.py: the basis of a heat
+source is evaluated in float64 and rounded once.  (A fused multiply-add is fmaf's, correctly rounded: tests/fma_ref.py.)  So the tests compare
   * outside every heat source's support: bit for bit, temperature and velocity, and
   * inside: rel-L2 < 1e-6, the project's figure for exp2 in fp32 against float64 (tests/test_gpu_emitters.py),
 and they assert first (emitter_ref.near_threshold) that no cell's basis sits so close to e^-4 that an ulp of exp2 decides its side.
@@ -11,9 +10,9 @@ Layouts as Fluid.upload / download: velocity float32[3][Z][Y][X], colour float32
 import numpy as np
 
 import emitter_ref as er
+from fma_ref import fma
 
 f32, f64 = np.float32, np.float64
-fma = er.fma
 
 # Where the tests put their heat sources: the six (centre, radius) pairs SIX of tests/test_gpu_emitters.py (tests/test_gpu_buoyancy.py asserts
 # that the two agree) -- the built-in ball's place, one well inside, one clipped by two walls, one more, the whole grid, one without a cell --

@@ -1,14 +1,15 @@
 """numpy model of the emitter pass (include/fluidx_hip.h fx_set_emitters, fluidx12_amd/csrc/fx_emit.hip: k_emit).
 
-The pass in fp32, operation by operation, with two liberties: exp2 is evaluated in float64 and rounded once, and a fused multiply-add is
-the float64 product (exact for two float32 factors) plus the float64 addend, rounded to float64 and then to float32.  Both differ from
-the device by an ulp here and there, so the tests compare
+The pass in fp32, operation by operation, with one liberty: exp2 is evaluated in float64 and rounded once, which differs from the device by
+an ulp here and there.  (A fused multiply-add is fmaf's, correctly rounded: tests/fma_ref.py.)  So the tests compare
   * outside every emitter's support: bit for bit (the cell is unchanged), and
   * inside: rel-L2 < 1e-6, the figure tests/test_gpu_sim.py::test_advect_matches_oracle uses for the built-in ball,
 and they assert first (near_threshold) that no cell's basis sits so close to the threshold e^-4 that an ulp of exp2 decides its side.
 
 Layouts as Fluid.upload / download: velocity float32[3][Z][Y][X], colour float32[Z][Y][X][4]."""
 import numpy as np
+
+from fma_ref import fma
 
 f32, f64 = np.float32, np.float64
 THRESHOLD = f32(0.0183156393)        # e^-4 as the kernels spell it
@@ -17,10 +18,6 @@ LOG2E = f32(1.44269502)
 # the reference's built-in impulse as an emitter (Impulse.hlsli, CSAdvect.hlsl:59-68)
 BUILTIN_3D = dict(center=(0.5, f32(0.1), 0.5), radius=1.0 / 16, color_rate=(8.0, 16.0, 40.0, 40.0), force=(0.0, 192.0, 0.0), swirl=200.0)
 BUILTIN_2D = dict(center=(0.5, f32(0.1), 0.5), radius=1.0 / 32, color_rate=(8.0, 16.0, 40.0, 40.0), force=(0.0, 48.0, 0.0), swirl=0.0)
-
-
-def fma(a, b, c):
-    return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
 
 
 def emitter(center, radius, color_rate=(8.0, 16.0, 40.0, 40.0), force=(0.0, 192.0, 0.0), swirl=200.0):

@@ -1,8 +1,8 @@
 """numpy model of the MacCormack advection (include/fluidx_hip.h fx_set_advection_scheme, fluidx12_amd/csrc/fx_maccormack.hip: k_mc_predict,
 k_mc_correct).
 
-Rules 1-5 of the header comment in fp32, operation by operation, with the conventions of tests/buoyancy_ref.py and tests/emitter_ref.py: `fma`,
-`lerp`, `addr_tap`, `cell_centres` and `sample` (k_advect's trace and colour sampler) are theirs, and the built-in impulse is emitter_ref's
+Rules 1-5 of the header comment in fp32, operation by operation, with the conventions of tests/buoyancy_ref.py and tests/emitter_ref.py: `fma`
+(tests/fma_ref.py: fmaf, correctly rounded), `lerp`, `addr_tap`, `cell_centres` and `sample` (k_advect's trace and colour sampler) are theirs, and the built-in impulse is emitter_ref's
 BUILTIN_3D / BUILTIN_2D emitter, whose basis is evaluated in float64 and rounded once.  So the tests compare
   * outside the built-in ball's support (everywhere with the impulse off): bit for bit, velocity and colour, and
   * inside: rel-L2 < 1e-6, the project's figure for exp2 in fp32 against float64 (tests/test_gpu_emitters.py).
@@ -13,9 +13,10 @@ import numpy as np
 
 import buoyancy_ref as br
 import emitter_ref as er
+from fma_ref import fma
 
 f32, f64 = np.float32, np.float64
-fma, lerp, addr_tap, cell_centres, sample = er.fma, br.lerp, br.addr_tap, br.cell_centres, br.sample
+lerp, addr_tap, cell_centres, sample = br.lerp, br.addr_tap, br.cell_centres, br.sample
 
 
 def back_taps(q, u0, dt, address):

@@ -1,5 +1,5 @@
 """numpy model of the multigrid pressure solver (include/fluidx_hip.h fx_set_pressure_solver, fluidx12_amd/csrc/fx_multigrid.hip): the rules in
-fp32, every operation rounded as written, fused multiply-adds exact (open_ref.fma).
+fp32, every operation rounded as written, fused multiply-adds exact (fma_ref.fma).
 
   plan       the levels of a grid: level l + 1 halves every extent that is halved (X, Y, and Z of a 3-D grid) while each of them is even and >= 4
   smooth     p' = fma(omega, J - p, p),  J = ((((((L - b) + R) + U) + D) + F) + B) * INV6     (2-D: ((((L - b) + R) + U) + D) * 0.25)
@@ -15,7 +15,8 @@ import struct
 
 import numpy as np
 
-from open_ref import fma, INV6
+from fma_ref import fma
+from open_ref import INV6
 
 f32 = np.float32
 MAX_LEVELS = 12

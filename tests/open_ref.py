@@ -9,14 +9,14 @@ operation rounded as written.
 "Beyond an open face" = a stencil neighbour whose unclamped index is -1 or N on an axis whose face there is open.  With faces = 0 the first two
 are tests/obstacle_ref/ bit for bit and heat_apply is buoyancy_ref.apply (tests/test_open_ref.py holds them to that).
 
-The fused multiply-adds of the projection are exact here (`fma`: the float64 sum is rounded to odd before it is rounded to float32, so the
-two roundings cannot disagree with the one of fmaf).  The back-trace uses buoyancy_ref's fma, so that the weights come from the very t the
-temperature sampler of that file forms.
+The fused multiply-adds are fmaf's, correctly rounded (tests/fma_ref.py, the one every model uses: the float64 sum is rounded to odd before it
+is rounded to float32, so the two roundings cannot disagree with the one of fmaf).
 
 Layouts as Fluid.upload / download: velocity float32[3][Z][Y][X], colour float32[Z][Y][X][4], pressure, divergence and masks [Z][Y][X]."""
 import numpy as np
 
 import buoyancy_ref as br
+from fma_ref import fma
 
 f32, f64 = np.float32, np.float64
 
@@ -36,20 +36,6 @@ def face_sets(dims):
     """what the GPU tests run: each single face, Y_HI | X_LO, all legal faces"""
     singles = [X_LO, X_HI, Y_LO, Y_HI] + ([Z_LO, Z_HI] if dims[2] > 1 else [])
     return singles + [Y_HI | X_LO, legal_faces(dims)]
-
-
-def fma(a, b, c):
-    """fmaf: float32 factors multiply exactly in float64; the sum is rounded to odd, then once to float32"""
-    p = np.asarray(a, f64) * np.asarray(b, f64)
-    c = np.asarray(c, f64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        s = p + c
-        bb = s - p
-        e = (p - (s - bb)) + (c - bb)                         # TwoSum: p + c = s + e exactly
-        even = (np.asarray(s).view(np.int64) & 1) == 0
-        fix = np.isfinite(s) & (e != 0) & even
-        s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
-    return s.astype(f32)
 
 
 def _shift(a, axis, d):

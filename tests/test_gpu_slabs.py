@@ -751,16 +751,22 @@ def test_bench_reference_configuration_line():
     assert d["cpu_baseline"]["value"] > 0 and "reference configuration" in d["cpu_baseline"]["sample"]
 
 
-@pytest.mark.parametrize("overlap", [2, 0])
-def test_slabs_with_lds_advection(overlap, knob):
+# (overlap, grid, storage).  The first two keep their ids; behind them a grid whose tiles are ragged in x and y (72 x 72: a second x tile of 8
+# lanes, general addressing, chunks of max(8, ..) planes) and fp16 storage -- like every test here on the shared-stream and on the peer group
+LDS_SLAB_CASES = [(2, (64, 64, 96), "fp32"), (0, (64, 64, 96), "fp32")] + [(o, d, st) for d, st in (((72, 72, 96), "fp32"), ((64, 64, 96), "fp16")) for o in (2, 0)]
+
+
+@pytest.mark.parametrize("overlap,dims,storage", LDS_SLAB_CASES,
+                         ids=[str(c[0]) if k < 2 else "%s-%s-%d" % ("x".join(map(str, c[1])), c[2], c[0]) for k, c in enumerate(LDS_SLAB_CASES)])
+def test_slabs_with_lds_advection(overlap, dims, storage, knob):
     """k_advect_lds inside the slab schedule (interior range with own-planes-only back-traces, full range after the exchange,
-    halo planes as the ring's z-1 / z+1): equal to the single domain advected by k_advect_fast, bit for bit"""
-    dims = (64, 64, 96)
+    halo planes as the ring's z-1 / z+1): equal to the single domain advected by k_advect_fast (72 x 72: k_advect), bit for bit"""
     knob("ADVECT_LDS", "0")
-    ref = run_single(dims, 6, jacobi_iters=10)
+    ref = run_single(dims, 6, jacobi_iters=10, storage=storage)
     want = (ref.download(fx.FIELD_VELOCITY), ref.download(fx.FIELD_COLOR), ref.download(fx.FIELD_PRESSURE))
+    assert want[1].any()
     knob("ADVECT_LDS", "2")
-    fl = run_slabs(dims, 6, 2, jacobi_iters=10, halo_jacobi=4, halo_advect=6, overlap=overlap)
+    fl = run_slabs(dims, 6, 2, jacobi_iters=10, halo_jacobi=4, halo_advect=6, overlap=overlap, storage=storage)
     assert np.array_equal(gather(fl, fx.FIELD_VELOCITY, 1), want[0])
     assert np.array_equal(gather(fl, fx.FIELD_COLOR, 0), want[1])
     assert np.array_equal(gather(fl, fx.FIELD_PRESSURE, 0), want[2])

@@ -94,8 +94,14 @@ def test_the_exact_fma_is_fmaf():
     a, b = f32(1 + 2.0 ** -12), f32(1 + 2.0 ** -12)                     # a * b = 1 + 2^-11 + 2^-24: exactly half an ulp above 1 + 2^-11 ...
     c = f32(2.0 ** -60)                                                  # ... and a hair more: fmaf rounds up, the float64 sum rounds to the tie first
     want = f32(1 + 2.0 ** -11 + 2.0 ** -23)
-    assert orf.fma(a, b, c) == want and br.fma(a, b, c) != want
+    twice = (np.float64(a) * np.float64(b) + np.float64(c)).astype(f32)    # the float64 sum rounded to float64, then to float32
+    assert orf.fma(a, b, c) == want and twice != want
     assert orf.fma(a, b, -c) == f32(1 + 2.0 ** -11)
+    import emitter_ref as er
+    import fma_ref
+    import maccormack_ref as mr
+    import multigrid_ref as mg
+    assert all(m.fma is fma_ref.fma for m in (orf, br, er, mr, mg))         # one fma for every model (tests/test_fma_ref.py: == libm's fmaf)
 
 
 @pytest.mark.parametrize("dims", [(20, 20, 5), (36, 36, 1)])
