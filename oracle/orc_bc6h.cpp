@@ -7,7 +7,10 @@
 // functional spec (mode table, partition/anchor tables, unquantisation, interpolation weights, the x * 31 / 64 finish) and
 // the DDS header layout of the DirectX documentation.  Pinned by known-answer blocks, by the decoder agreeing with itself
 // across the asset's mip chain (mip n+1 is a box filter of mip n to within BC6H quantisation, encoded in other modes and
-// partitions) and by the HIP decoder matching it bit for bit on random blocks (every 128-bit pattern is a defined block).
+// partitions), by an independent decoder (Pillow's, recorded in tests/golden/bc6h_independent.npz for every two-region mode x
+// partition, the one-region and reserved modes and 2048 random blocks: within one 8-bit step on values below 1, saturated at the
+// same values -- tests/test_probe_edges.py) and by the HIP decoder matching it bit for bit on random blocks (every 128-bit
+// pattern is a defined block).
 #include "orc_common.h"
 #include "fx_oracle.h"
 #include <string>

@@ -1,6 +1,5 @@
 """k_bc6h_decode + the DDS parser behind fx_dds_decode_cube (row f-4) against the oracle, bit for bit."""
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -8,18 +7,16 @@ import pytest
 import fluidx12_amd as fx
 from oracle import orc
 
+import probe_edges as pe
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIX = np.load(os.path.join(GOLD, "bc6h_fixture.npz"))
 
 
 def make_dds(blocks_per_face, n):
-    """a DDS cube map (DX10 header, BC6H_UF16, one mip) around 6 x (n/4)^2 given blocks; header taken from the fixture"""
-    hdr = bytearray(FIX["dds_mip3"].tobytes()[:148])
-    struct.pack_into("<I", hdr, 12, n)
-    struct.pack_into("<I", hdr, 16, n)
-    struct.pack_into("<I", hdr, 20, ((n + 3) // 4) ** 2 * 16)
-    return bytes(hdr) + np.ascontiguousarray(blocks_per_face, np.uint8).tobytes()
+    """a DDS cube map (DX10 header, BC6H_UF16, one mip) around 6 x (n/4)^2 given blocks"""
+    return pe.bc6h_cube_dds(n, [blocks_per_face])
 
 
 def probe():
@@ -71,36 +68,12 @@ def test_malformed_containers_are_rejected():
 
 def dds_cube(cube, fmt, mips=1, legacy=False):
     """a DDS cube map around cube[6][n][n][3] floats in an uncompressed format (with its mip chain made by 2 x 2 box filters)"""
-    n = cube.shape[1]
     chain = [cube]
     for _ in range(1, mips):
         c = chain[-1]
         chain.append(c.reshape(6, c.shape[1] // 2, 2, c.shape[2] // 2, 2, 3).mean(axis=(2, 4)).astype(np.float32))
 
-    def enc(c):
-        rgba = np.concatenate([c, np.ones(c.shape[:-1] + (1,), np.float32)], axis=-1)
-        if fmt == "rgba32f":
-            return rgba.astype("<f4").tobytes()
-        if fmt == "rgb32f":
-            return c.astype("<f4").tobytes()
-        if fmt == "rgba16f":
-            return rgba.astype("<f2").tobytes()
-        return np.rint(np.clip(rgba, 0, 1) * 255).astype(np.uint8).tobytes()
-
-    hdr = bytearray(128)
-    hdr[0:4] = b"DDS "
-    struct.pack_into("<IIIII", hdr, 4, 124, 0x1007 | (0x20000 if mips > 1 else 0), n, n, 0)
-    struct.pack_into("<I", hdr, 28, mips)
-    struct.pack_into("<II", hdr, 76, 32, 4)                            # DDS_PIXELFORMAT: size, DDPF_FOURCC
-    struct.pack_into("<II", hdr, 108, 0x1008 | (0x400000 if mips > 1 else 0), 0xFE00)   # caps: complex | texture (| mipmap); caps2: cube map, all faces
-    if legacy:
-        struct.pack_into("<I", hdr, 84, {"rgba16f": 113, "rgba32f": 116}[fmt])
-        extra = b""
-    else:
-        hdr[84:88] = b"DX10"
-        extra = struct.pack("<IIIII", {"rgba32f": 2, "rgb32f": 6, "rgba16f": 10, "rgba8": 28}[fmt], 3, 4, 1, 0)
-    body = b"".join(b"".join(enc(c[f]) for c in chain) for f in range(6))
-    return bytes(hdr) + extra + body, chain
+    return pe.linear_cube_dds(chain, fmt, legacy=legacy), chain
 
 
 @pytest.mark.parametrize("fmt,legacy", [("rgba32f", False), ("rgb32f", False), ("rgba16f", False), ("rgba8", False), ("rgba16f", True), ("rgba32f", True)])
