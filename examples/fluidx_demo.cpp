@@ -5,6 +5,8 @@
 // Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
 //        [-emitter CX CY CZ R]... [-noimpulse]     (smoke sources, fx_set_emitters: texture space [0,1]^3, with the built-in's colour and lift; -noimpulse: without the reference's own source)
 //        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; the demo does not draw the ball itself)
+//        [-obstacleVelocity VX VY VZ]     (the ball moves: each frame it is voxelised anew at c + v * t, stopping at the walls, under one body with that velocity,
+//                                          fx_set_obstacle_bodies: texture units per unit time; it then pushes the smoke in front of it and drags a wake)
 //        [-openWalls BITS]     (faces through which the smoke leaves, fx_set_open_walls: 1 x-, 2 x+, 4 y-, 8 y+ (up), 16 z-, 32 z+; accepts 0x.. too)
 //        [-advection maccormack|semi-lagrangian]     (the advection scheme, fx_set_advection_scheme; default: the reference's semi-Lagrangian step)
 //        [-multigrid]     (the pressure solve as two multigrid V(2,2) cycles instead of the Jacobi sweeps, fx_set_pressure_solver)
@@ -102,6 +104,8 @@ int main(int argc, char** argv)
 	bool noImpulse = false;
 	bool obstacleSet = false;                           // not in the reference: its only boundaries are the box's walls
 	float obstacle[4] = {};
+	bool obstacleMoves = false;
+	float obstacleVelocity[3] = {};
 	uint32_t openWalls = 0;                             // not in the reference: its box is closed on all six faces
 	uint32_t advection = FX_ADVECT_SEMI_LAGRANGIAN;     // not in the reference: its advection is semi-Lagrangian
 	bool multigrid = false;                             // not in the reference: its pressure solve is Jacobi sweeps
@@ -126,6 +130,7 @@ int main(int argc, char** argv)
 		}
 		else if (!std::strcmp(argv[i], "-noimpulse")) noImpulse = true;
 		else if (!std::strcmp(argv[i], "-obstacle") && i + 4 < argc) { for (float& v : obstacle) v = (float)atof(argv[++i]); obstacleSet = true; }
+		else if (!std::strcmp(argv[i], "-obstacleVelocity") && i + 3 < argc) { for (float& v : obstacleVelocity) v = (float)atof(argv[++i]); obstacleMoves = true; }
 		else if (!std::strcmp(argv[i], "-openWalls") && i + 1 < argc) openWalls = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
 		else if (!std::strcmp(argv[i], "-advection") && i + 1 < argc) {
 			const char* v = argv[++i];
@@ -140,7 +145,9 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-ambient") && i + 4 < argc) { for (float& v : ambient) v = (float)atof(argv[++i]); ambientSet = lightSet = true; }
 	}
 	Fluid fluid;
-	if (!fluid.Init(nullptr, width, height, grid)) {   // ThrowIfFailed(E_FAIL) in the reference (FluidX12.cpp:198-200)
+	Fluid::Options options;
+	if (obstacleSet) options.jacobiMode = FX_JACOBI_FIXED;   // obstacles are served by the fixed-count solve only (fx_set_obstacles refuses the per-cell early-out)
+	if (!fluid.Init(nullptr, width, height, grid, options)) {   // ThrowIfFailed(E_FAIL) in the reference (FluidX12.cpp:198-200)
 		std::fprintf(stderr, "Fluid::Init failed: %s\n", fx_error_string(fluid.LastStatus()));
 		return 1;
 	}
@@ -154,17 +161,35 @@ int main(int argc, char** argv)
 	}
 	if (!emitters.empty() && !fluid.SetEmitters(emitters)) { std::fprintf(stderr, "-emitter: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (noImpulse && !fluid.SetImpulse(false)) { std::fprintf(stderr, "-noimpulse: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
-	if (obstacleSet) {                                  // voxelise: the cells whose centre lies inside the ball
+	// voxelise: the cells whose centre lies inside the ball at c + v * t, t clamped per axis where the ball meets a wall; with a velocity also the
+	// one body whose box encloses the ball (an axis on which the ball has stopped no longer moves)
+	auto placeObstacle = [&](float t) {
+		float c[3], v[3];
+		for (int a = 0; a < 3; ++a) {
+			const float lo = std::min(obstacle[3], 0.5f), hi = 1.0f - lo, at = obstacle[a] + obstacleVelocity[a] * t;
+			c[a] = std::min(std::max(at, std::min(lo, obstacle[a])), std::max(hi, obstacle[a]));
+			v[a] = c[a] == at ? obstacleVelocity[a] : 0.0f;
+		}
 		std::vector<uint8_t> solid((size_t)grid.x * grid.y * grid.z, 0);
 		for (uint32_t z = 0; z < grid.z; ++z)
 			for (uint32_t y = 0; y < grid.y; ++y)
 				for (uint32_t x = 0; x < grid.x; ++x) {
-					const float dx = (x + 0.5f) / grid.x - obstacle[0], dy = (y + 0.5f) / grid.y - obstacle[1];
-					const float dz = grid.z > 1 ? (z + 0.5f) / grid.z - obstacle[2] : 0.0f;
+					const float dx = (x + 0.5f) / grid.x - c[0], dy = (y + 0.5f) / grid.y - c[1];
+					const float dz = grid.z > 1 ? (z + 0.5f) / grid.z - c[2] : 0.0f;
 					solid[((size_t)z * grid.y + y) * grid.x + x] = dx * dx + dy * dy + dz * dz <= obstacle[3] * obstacle[3] ? 1 : 0;
 				}
-		if (!fluid.SetObstacles(solid)) { std::fprintf(stderr, "-obstacle: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
-	}
+		if (!fluid.SetObstacles(solid)) return false;
+		if (!obstacleMoves) return true;
+		fx_obstacle_body body = {};
+		body.struct_size = sizeof body;
+		for (int a = 0; a < 3; ++a) {
+			body.box_lo[a] = c[a] - obstacle[3]; body.box_hi[a] = c[a] + obstacle[3];
+			body.linear[a] = v[a]; body.pivot[a] = c[a];
+		}
+		return fluid.SetObstacleBodies(&body, 1);
+	};
+	if (obstacleMoves && !obstacleSet) { std::fprintf(stderr, "-obstacleVelocity: there is no -obstacle to move\n"); return 1; }
+	if (obstacleSet && !placeObstacle(0.0f)) { std::fprintf(stderr, "-obstacle: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (openWalls && !fluid.SetOpenWalls(openWalls)) { std::fprintf(stderr, "-openWalls 0x%x: %s\n", (unsigned)openWalls, fx_error_string(fluid.LastStatus())); return 1; }
 	if (advection != FX_ADVECT_SEMI_LAGRANGIAN && !fluid.SetAdvectionScheme(advection)) { std::fprintf(stderr, "-advection: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (multigrid) {
@@ -193,6 +218,7 @@ int main(int argc, char** argv)
 	const auto t0 = std::chrono::steady_clock::now();
 	for (uint32_t f = 0; f < frames; ++f) {
 		const uint8_t frameIndex = f % Fluid::FrameCount;
+		if (obstacleMoves && f > 0 && !placeObstacle(f * timeStep)) { std::fprintf(stderr, "frame %u, -obstacleVelocity: %s\n", f, fx_error_string(fluid.LastStatus())); return 1; }
 		fluid.UpdateFrame(timeStep, frameIndex, view, proj, eyePt);
 		fluid.Simulate(nullptr, frameIndex);
 		const float clearColor[4] = { 0.2f, 0.2f, 0.2f, 0.0f };                    // FluidX12.cpp:471-472

@@ -26,6 +26,7 @@ DEPTH_DEVICE = 0x1                   # fx_set_scene_depth: the depth buffer is d
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
 OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memory
+MAX_OBSTACLE_BODIES = 16             # FX_MAX_OBSTACLE_BODIES
 MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
 WALL_X_LO, WALL_X_HI, WALL_Y_LO, WALL_Y_HI, WALL_Z_LO, WALL_Z_HI = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20   # FX_WALL_*: fx_set_open_walls
 WALL_ALL = 0x3F
@@ -57,6 +58,11 @@ class Light(C.Structure):
 class Emitter(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_float * 3), ("radius", C.c_float),
                 ("color_rate", C.c_float * 4), ("force", C.c_float * 3), ("swirl", C.c_float)]
+
+
+class ObstacleBody(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
+                ("linear", C.c_float * 3), ("angular", C.c_float * 3), ("pivot", C.c_float * 3)]
 
 
 class Buoyancy(C.Structure):
@@ -119,6 +125,8 @@ SYMBOLS = {
     "fx_set_obstacles": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32]),
     "fx_get_obstacles": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     "fx_enforce_obstacles": (C.c_int, [_vp, _vp]),
+    "fx_set_obstacle_bodies": (C.c_int, [_vp, C.POINTER(ObstacleBody), C.c_uint32]),
+    "fx_get_obstacle_bodies": (C.c_int, [_vp, C.POINTER(ObstacleBody), C.c_uint32, C.POINTER(C.c_uint32)]),
     "fx_set_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy)]),
     "fx_get_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy), C.POINTER(C.c_int)]),
     "fx_set_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32]),

@@ -146,6 +146,19 @@ public:
 	// the enforce stage alone (fx_enforce_obstacles), beside Emit
 	bool EnforceObstacles(void* stream = nullptr) { m_status = fx_enforce_obstacles(m_ctx, stream); return m_status == FX_OK; }
 
+	// the rigid-body velocities of the solids under the mask (fx_set_obstacle_bodies; count 0 = every solid rests, the default): a moving
+	// object is a new mask and a new list per frame, and then pushes the smoke in front of it and drags it behind
+	bool SetObstacleBodies(const fx_obstacle_body* list, uint32_t count) { m_status = fx_set_obstacle_bodies(m_ctx, list, count); return m_status == FX_OK; }
+	bool SetObstacleBodies(const std::vector<fx_obstacle_body>& list) { return SetObstacleBodies(list.data(), (uint32_t)list.size()); }
+	bool GetObstacleBodies(std::vector<fx_obstacle_body>& out)
+	{
+		uint32_t n = 0;
+		out.resize(FX_MAX_OBSTACLE_BODIES);
+		m_status = fx_get_obstacle_bodies(m_ctx, out.data(), FX_MAX_OBSTACLE_BODIES, &n);
+		out.resize(m_status == FX_OK ? n : 0);
+		return m_status == FX_OK;
+	}
+
 	// not in the reference (its box is closed): the faces through which the smoke leaves (fx_set_open_walls; FX_WALL_* bits, 0 = all closed,
 	// the default) and the inflow stage alone (fx_open_inflow), directly behind the advection, beside Emit
 	bool SetOpenWalls(uint32_t faces) { m_status = fx_set_open_walls(m_ctx, faces); return m_status == FX_OK; }

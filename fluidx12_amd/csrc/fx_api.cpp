@@ -525,6 +525,34 @@ int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* so
 
 int fx_enforce_obstacles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, enforce_phase); }
 
+// ---- the solids' rigid-body velocities (fx_obstacle_moving.hip): a host-side list like the emitters ---------------------------------
+int fx_set_obstacle_bodies(fx_ctx* ctx, const fx_obstacle_body* list, uint32_t count)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // on the obstacles' footing: fx_set_obstacles refuses these contexts
+	if (count > FX_MAX_OBSTACLE_BODIES || (count && !list)) return FX_E_INVALID;
+	for (uint32_t k = 0; k < count; ++k) {
+		const fx_obstacle_body& b = list[k];
+		if (b.struct_size != sizeof(fx_obstacle_body) || b.flags != 0) return FX_E_INVALID;
+		for (int a = 0; a < 3; ++a) {
+			if (!std::isfinite(b.box_lo[a]) || !std::isfinite(b.box_hi[a]) || !std::isfinite(b.linear[a]) || !std::isfinite(b.angular[a]) ||
+				!std::isfinite(b.pivot[a])) return FX_E_INVALID;
+			if (b.box_lo[a] > b.box_hi[a]) return FX_E_INVALID;
+		}
+	}
+	ctx->obst_bodies.assign(list, list + count);
+	return FX_OK;
+}
+
+int fx_get_obstacle_bodies(fx_ctx* ctx, fx_obstacle_body* out, uint32_t capacity, uint32_t* count)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;             // (slab ranks may ask: the list is empty there)
+	if (!count || (capacity && !out)) return FX_E_INVALID;
+	*count = (uint32_t)ctx->obst_bodies.size();
+	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->obst_bodies[k];
+	return FX_OK;
+}
+
 // ---- open walls (fx_open.hip) ---------------------------------------------------------------------------
 int fx_set_open_walls(fx_ctx* ctx, uint32_t faces)
 {

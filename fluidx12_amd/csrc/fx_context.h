@@ -69,6 +69,9 @@ struct fx_ctx {
 	unsigned* obst_stats = nullptr; // device, 8 words: what k_obstacle_codes counts
 	uint64_t obst_cells = 0;        // solid cells
 	int obst_lo[3] = { 0, 0, 0 }, obst_hi[3] = { 0, 0, 0 };   // their bounding box [lo, hi): what the enforce launch covers
+	// the solids' rigid-body velocities (fx_set_obstacle_bodies; configuration on the same terms): a solid cell belongs to the first body whose
+	// box holds its centre.  In force while obst_code is set and the list is not empty: the moving kernels (fx_obstacle_moving.hip) then run
+	std::vector<fx_obstacle_body> obst_bodies;   // may be set with no mask in force; empty = every solid rests (default)
 	// open walls (fx_set_open_walls; configuration on the same terms): FX_WALL_* bits, 0 = all six faces closed: every launch is today's
 	uint32_t open_faces = 0;
 	// buoyancy (fx_set_buoyancy / fx_set_heat_sources; configuration on the same terms): the temperature ping-pong pair, fp32 whatever the storage,

@@ -180,6 +180,17 @@ hipError_t launch_jacobi_bnd(const Geom& g, const float* p_in, const float* b, c
 	int z_begin, int z_end, hipStream_t s);
 hipError_t launch_project_bnd(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
 	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
+// ---- solids that move (fx_obstacle_moving.hip; fx_set_obstacle_bodies), whole grids only: the three obstacle launches whose rule sees the
+// solid's velocity, taken while a mask is in force and the list is not empty (count >= 1, code not null: else hipErrorInvalidValue).  The
+// sweeps are launch_jacobi_bnd's either way.  BodyArgs is what the kernels get: the list by value, and whether the grid is 3-D
+struct BodyArg { float lo[3], hi[3], lin[3], ang[3], piv[3]; };
+struct BodyArgs { int n, is3d; BodyArg b[FX_MAX_OBSTACLE_BODIES]; };
+hipError_t launch_obstacle_enforce_mov(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3],
+	const fx_obstacle_body* list, int count, void* vel, void* col, float* alpha, hipStream_t s);
+hipError_t launch_divergence_obs_mov(const Geom& g, int half_store, const void* vel, const uint8_t* code, const fx_obstacle_body* list, int count,
+	float* b, int z_begin, int z_end, hipStream_t s);
+hipError_t launch_project_bnd_mov(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
+	const fx_obstacle_body* list, int count, void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

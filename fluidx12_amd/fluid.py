@@ -335,6 +335,37 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_enforce_obstacles(self._ctx, stream), "EnforceObstacles")
 
+    def SetObstacleBodies(self, bodies):
+        """the rigid-body velocities of the solids under the mask (fx_set_obstacle_bodies): a sequence of dicts (or capi.ObstacleBody) with
+        "box_lo" and "box_hi" (x, y, z) in texture space [0, 1]^3 -- the solid cells whose centre lies in the closed box belong to the body,
+        the first body in list order wins -- and optionally "linear" (the pivot's velocity, texture units per unit time), "angular" (radians
+        per unit time about the pivot) and "pivot" (default: the box's centre); a missing vector is zero.  None or () = every solid rests
+        (default).  Takes effect while a mask is set (SetObstacles), in either order.  Configuration: kept across UpdateFrame, not stored
+        in checkpoints.  Whole-grid, fixed-mode contexts only."""
+        self._need()
+        items = list(bodies or ())
+        arr = (capi.ObstacleBody * max(len(items), 1))()
+        for k, b in enumerate(items):
+            if isinstance(b, capi.ObstacleBody):
+                arr[k] = b
+                continue
+            lo, hi = [float(v) for v in b["box_lo"]], [float(v) for v in b["box_hi"]]
+            arr[k].struct_size, arr[k].flags = C.sizeof(capi.ObstacleBody), int(b.get("flags", 0))
+            arr[k].box_lo, arr[k].box_hi = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+            arr[k].linear = (C.c_float * 3)(*[float(v) for v in b.get("linear", (0.0, 0.0, 0.0))])
+            arr[k].angular = (C.c_float * 3)(*[float(v) for v in b.get("angular", (0.0, 0.0, 0.0))])
+            arr[k].pivot = (C.c_float * 3)(*[float(v) for v in b.get("pivot", [0.5 * (l + h) for l, h in zip(lo, hi)])])
+        capi.check(self._lib.fx_set_obstacle_bodies(self._ctx, arr if items else None, len(items)), "SetObstacleBodies")
+
+    def GetObstacleBodies(self):
+        """the list in force (fx_get_obstacle_bodies), as dicts with the keys SetObstacleBodies takes"""
+        self._need()
+        n = C.c_uint32(0)
+        arr = (capi.ObstacleBody * capi.MAX_OBSTACLE_BODIES)()
+        capi.check(self._lib.fx_get_obstacle_bodies(self._ctx, arr, capi.MAX_OBSTACLE_BODIES, C.byref(n)), "GetObstacleBodies")
+        return [{"box_lo": tuple(b.box_lo), "box_hi": tuple(b.box_hi), "linear": tuple(b.linear), "angular": tuple(b.angular),
+                 "pivot": tuple(b.pivot), "flags": b.flags} for b in arr[:n.value]]
+
     def SetOpenWalls(self, faces):
         """the faces of the box through which the smoke leaves (fx_set_open_walls): a set of capi.WALL_* bits, 0 = all closed (default).  Beyond
         an open face the pressure is 0, the smoke is clear air and the temperature ambient; the projection does not damp flow towards it.

@@ -368,6 +368,49 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells);
 int fx_enforce_obstacles(fx_ctx* ctx, void* stream);
 
+/* Solids that move: rigid-body velocities for the voxel mask (the other half of the Harris / Crane et al. scheme: the solid's velocity enters
+ * the divergence and the boundary rule of the projection).  The mask stays what it is -- any non-zero byte is solid, and a moving object is a
+ * new fx_set_obstacles per frame --; fx_set_obstacle_bodies says how fast the solids under it move, so that they push the air in front of
+ * them and drag it behind them.  A body claims solid cells by a box: with pos_a(n) = ((float)i_a + 0.5f) / (float)N_a, the advection's cell
+ * centre, B(n) = the first body of the list with box_lo[a] <= pos_a(n) && pos_a(n) <= box_hi[a] on every axis (a 2-D grid ignores z); none if
+ * no box holds the cell.  With r = pos(n) - pivot the velocity of solid cell n is w(n) = linear + angular x r, in this order:
+ *   w_x = fmaf(angular_y, r_z, fmaf(-angular_z, r_y, linear_x))
+ *   w_y = fmaf(angular_z, r_x, fmaf(-angular_x, r_z, linear_y))
+ *   w_z = fmaf(angular_x, r_y, fmaf(-angular_y, r_x, linear_z))
+ *   2-D grids: only angular_z acts: w_x = fmaf(-angular_z, r_y, linear_x), w_y = fmaf(angular_z, r_x, linear_y), w_z = +0
+ *   w(n) = +0 where B(n) is none: a solid in no box rests
+ * S and the clamped neighbours n-a / n+a are those of the obstacle block above, and so is every operation not named here:
+ *   enforce     a solid cell's VELOCITY1 becomes w(c), rounded once to the storage; its COLOR (and the render's alpha) become +0 as before
+ *   divergence  v_a(n) read as S(n) ? w_a(n) : v_a(n) (w in fp32, not as stored); b = 0 in a solid cell
+ *   relaxation  unchanged: the pressure ghost of a moving wall is still the cell's own pressure
+ *   projection  the gradient as before; then, where S(n-a) | S(n+a): u[a] = 0.5f * (w_a(n-a) + w_a(n+a)) if both are solid, otherwise the one
+ *               solid neighbour's w_a (free slip against a moving wall: the normal component is the wall's); then the wall damping, with the
+ *               open-face exception of fx_set_open_walls; a solid cell's three components become w(c)
+ *   the other stages (heat, inflow, emitters, confinement, both advection schemes) are unchanged: they see the bodies only through the
+ *               velocity the enforce pass and the projection leave in solid cells -- the advection's taps into a solid drag the air with it
+ * (tests/moving_obstacle_ref.py restates the rules in numpy.)  Velocities are in texture units per unit time, the unit of FX_FIELD_VELOCITY
+ * (the advection traces pos - v * dt).  A rotation given in texture space is rigid in world space only on axes of equal extent: on a grid
+ * whose box is no cube the caller scales angular and pivot per axis pair, or accepts the shear.
+ * The list is configuration on the emitters' terms: a host-side list per context (it travels with the launches: no device memory, no copy),
+ * kept across fx_update_frame, not checkpointed, not part of fx_field_digest.  count 0 (list may be NULL) is the default, "every solid
+ * rests": every call then runs exactly the launches it runs without this function.  The list may be set with or without a mask in force and
+ * takes effect once one is (as heat sources wait for buoyancy); it does not depend on the order of the two calls.  A cell inside several
+ * boxes belongs to the first body in list order.  The library neither moves nor rasterises the mask, and no force acts on the body.
+ * fx_set_obstacle_bodies: FX_E_INVALID, the previous list staying in force, for count > FX_MAX_OBSTACLE_BODIES, count with a NULL list, a wrong
+ * struct_size, non-zero flags, a non-finite member, box_lo[a] > box_hi[a], a context that owns fewer planes than the grid (slab ranks of every
+ * transport) and FX_JACOBI_FAITHFUL contexts (fx_set_obstacles refuses them too); FX_E_STATE for FX_FLAG_RENDER_ONLY.
+ * fx_get_obstacle_bodies: as fx_get_emitters (slab ranks may ask: the list is empty there). */
+#define FX_MAX_OBSTACLE_BODIES 16u
+typedef struct fx_obstacle_body {
+	uint32_t struct_size, flags;   /* sizeof(fx_obstacle_body) = 68; flags must be 0 */
+	float box_lo[3], box_hi[3];    /* texture space: the solid cells whose CENTRE lies in this closed box belong to the body */
+	float linear[3];               /* velocity of the pivot, texture units per unit time */
+	float angular[3];              /* angular velocity about the pivot, radians per unit time, texture space */
+	float pivot[3];                /* texture space */
+} fx_obstacle_body;
+int fx_set_obstacle_bodies(fx_ctx* ctx, const fx_obstacle_body* list, uint32_t count);
+int fx_get_obstacle_bodies(fx_ctx* ctx, fx_obstacle_body* out, uint32_t capacity, uint32_t* count);
+
 /* Open walls (no reference counterpart: the reference's box is closed on all six faces -- the clamped neighbour indices of its stages and the
  * wall damping of its projection).  fx_set_open_walls names the faces through which the smoke may leave; the step is then
  *   advect -> inflow -> emit -> heat -> enforce -> confine -> divergence -> relaxation -> projection.
