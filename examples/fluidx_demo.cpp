@@ -7,6 +7,8 @@
 //        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; the demo does not draw the ball itself)
 //        [-obstacleVelocity VX VY VZ]     (the ball moves: each frame it is voxelised anew at c + v * t, stopping at the walls, under one body with that velocity,
 //                                          fx_set_obstacle_bodies: texture units per unit time; it then pushes the smoke in front of it and drags a wake)
+//        [-obstacleMesh]     (the ball is handed over as a triangle mesh, fx_set_obstacle_meshes: a UV sphere of 16 x 32 segments built once and voxelised on the
+//                             device; a moving ball is then moved by the mesh's transform alone, with no mask filled or uploaded per frame; 3-D grids)
 //        [-openWalls BITS]     (faces through which the smoke leaves, fx_set_open_walls: 1 x-, 2 x+, 4 y-, 8 y+ (up), 16 z-, 32 z+; accepts 0x.. too)
 //        [-advection maccormack|semi-lagrangian]     (the advection scheme, fx_set_advection_scheme; default: the reference's semi-Lagrangian step)
 //        [-multigrid]     (the pressure solve as two multigrid V(2,2) cycles instead of the Jacobi sweeps, fx_set_pressure_solver)
@@ -105,6 +107,7 @@ int main(int argc, char** argv)
 	bool obstacleSet = false;                           // not in the reference: its only boundaries are the box's walls
 	float obstacle[4] = {};
 	bool obstacleMoves = false;
+	bool obstacleMesh = false;
 	float obstacleVelocity[3] = {};
 	uint32_t openWalls = 0;                             // not in the reference: its box is closed on all six faces
 	uint32_t advection = FX_ADVECT_SEMI_LAGRANGIAN;     // not in the reference: its advection is semi-Lagrangian
@@ -131,6 +134,7 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-noimpulse")) noImpulse = true;
 		else if (!std::strcmp(argv[i], "-obstacle") && i + 4 < argc) { for (float& v : obstacle) v = (float)atof(argv[++i]); obstacleSet = true; }
 		else if (!std::strcmp(argv[i], "-obstacleVelocity") && i + 3 < argc) { for (float& v : obstacleVelocity) v = (float)atof(argv[++i]); obstacleMoves = true; }
+		else if (!std::strcmp(argv[i], "-obstacleMesh")) obstacleMesh = true;
 		else if (!std::strcmp(argv[i], "-openWalls") && i + 1 < argc) openWalls = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
 		else if (!std::strcmp(argv[i], "-advection") && i + 1 < argc) {
 			const char* v = argv[++i];
@@ -161,6 +165,32 @@ int main(int argc, char** argv)
 	}
 	if (!emitters.empty() && !fluid.SetEmitters(emitters)) { std::fprintf(stderr, "-emitter: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (noImpulse && !fluid.SetImpulse(false)) { std::fprintf(stderr, "-noimpulse: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	// -obstacleMesh: the unit UV sphere about the origin, 16 stacks of 32 slices with the poles on y, built once; the ball is its image under
+	// scale r, translate c
+	std::vector<float> ballPositions;
+	std::vector<uint32_t> ballIndices;
+	if (obstacleMesh) {
+		const uint32_t stacks = 16, slices = 32, south = 1 + (stacks - 1) * slices;
+		const float pi = 3.14159265358979f;
+		auto push = [&](float x, float y, float z) { ballPositions.push_back(x); ballPositions.push_back(y); ballPositions.push_back(z); };
+		auto ring = [&](uint32_t i, uint32_t j) { return 1 + (i - 1) * slices + j % slices; };
+		auto tri = [&](uint32_t a, uint32_t b, uint32_t c) { ballIndices.push_back(a); ballIndices.push_back(b); ballIndices.push_back(c); };
+		push(0.0f, 1.0f, 0.0f);
+		for (uint32_t i = 1; i < stacks; ++i)
+			for (uint32_t j = 0; j < slices; ++j) {
+				const float th = pi * i / stacks, ph = 2.0f * pi * j / slices;
+				push(std::sin(th) * std::cos(ph), std::cos(th), std::sin(th) * std::sin(ph));
+			}
+		push(0.0f, -1.0f, 0.0f);
+		for (uint32_t j = 0; j < slices; ++j) {
+			tri(0, ring(1, j), ring(1, j + 1));
+			tri(south, ring(stacks - 1, j + 1), ring(stacks - 1, j));
+			for (uint32_t i = 1; i + 1 < stacks; ++i) {
+				tri(ring(i, j), ring(i + 1, j), ring(i + 1, j + 1));
+				tri(ring(i, j), ring(i + 1, j + 1), ring(i, j + 1));
+			}
+		}
+	}
 	// voxelise: the cells whose centre lies inside the ball at c + v * t, t clamped per axis where the ball meets a wall; with a velocity also the
 	// one body whose box encloses the ball (an axis on which the ball has stopped no longer moves)
 	auto placeObstacle = [&](float t) {
@@ -170,15 +200,21 @@ int main(int argc, char** argv)
 			c[a] = std::min(std::max(at, std::min(lo, obstacle[a])), std::max(hi, obstacle[a]));
 			v[a] = c[a] == at ? obstacleVelocity[a] : 0.0f;
 		}
-		std::vector<uint8_t> solid((size_t)grid.x * grid.y * grid.z, 0);
-		for (uint32_t z = 0; z < grid.z; ++z)
+		if (obstacleMesh) {                                 // the library voxelises: 48 bytes of transform say where the ball is
+			const float m[12] = { obstacle[3], 0, 0, c[0], 0, obstacle[3], 0, c[1], 0, 0, obstacle[3], c[2] };
+			fx_mesh_report report = {};
+			if (!fluid.SetObstacleMesh(ballPositions, ballIndices, m, &report)) return false;
+			if (report.open_columns || report.skipped_triangles) std::fprintf(stderr, "-obstacleMesh: %u open columns, %u skipped triangles\n", report.open_columns, report.skipped_triangles);
+		}
+		std::vector<uint8_t> solid(obstacleMesh ? 0 : (size_t)grid.x * grid.y * grid.z, 0);
+		for (uint32_t z = 0; z < grid.z && !obstacleMesh; ++z)
 			for (uint32_t y = 0; y < grid.y; ++y)
 				for (uint32_t x = 0; x < grid.x; ++x) {
 					const float dx = (x + 0.5f) / grid.x - c[0], dy = (y + 0.5f) / grid.y - c[1];
 					const float dz = grid.z > 1 ? (z + 0.5f) / grid.z - c[2] : 0.0f;
 					solid[((size_t)z * grid.y + y) * grid.x + x] = dx * dx + dy * dy + dz * dz <= obstacle[3] * obstacle[3] ? 1 : 0;
 				}
-		if (!fluid.SetObstacles(solid)) return false;
+		if (!obstacleMesh && !fluid.SetObstacles(solid)) return false;
 		if (!obstacleMoves) return true;
 		fx_obstacle_body body = {};
 		body.struct_size = sizeof body;
@@ -188,6 +224,7 @@ int main(int argc, char** argv)
 		}
 		return fluid.SetObstacleBodies(&body, 1);
 	};
+	if (obstacleMesh && !obstacleSet) { std::fprintf(stderr, "-obstacleMesh: there is no -obstacle to hand over\n"); return 1; }
 	if (obstacleMoves && !obstacleSet) { std::fprintf(stderr, "-obstacleVelocity: there is no -obstacle to move\n"); return 1; }
 	if (obstacleSet && !placeObstacle(0.0f)) { std::fprintf(stderr, "-obstacle: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (openWalls && !fluid.SetOpenWalls(openWalls)) { std::fprintf(stderr, "-openWalls 0x%x: %s\n", (unsigned)openWalls, fx_error_string(fluid.LastStatus())); return 1; }

@@ -27,6 +27,8 @@ LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1   # fx_light.kind
 MAX_EMITTERS = 16                    # FX_MAX_EMITTERS
 OBSTACLES_DEVICE = 0x1               # fx_set_obstacles: the mask is device memory
 MAX_OBSTACLE_BODIES = 16             # FX_MAX_OBSTACLE_BODIES
+MAX_OBSTACLE_MESHES = 16             # FX_MAX_OBSTACLE_MESHES
+MESH_DEVICE = 0x1                    # FX_MESH_DEVICE: fx_obstacle_mesh's positions / indices / transform are device memory
 MAX_HEAT_SOURCES = 16                # FX_MAX_HEAT_SOURCES
 WALL_X_LO, WALL_X_HI, WALL_Y_LO, WALL_Y_HI, WALL_Z_LO, WALL_Z_HI = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20   # FX_WALL_*: fx_set_open_walls
 WALL_ALL = 0x3F
@@ -63,6 +65,15 @@ class Emitter(C.Structure):
 class ObstacleBody(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
                 ("linear", C.c_float * 3), ("angular", C.c_float * 3), ("pivot", C.c_float * 3)]
+
+
+class ObstacleMesh(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("positions", C.c_void_p), ("indices", C.c_void_p),
+                ("vertex_count", C.c_uint32), ("triangle_count", C.c_uint32), ("transform", C.c_void_p)]
+
+
+class MeshReport(C.Structure):
+    _fields_ = [("solid_cells", C.c_uint64), ("open_columns", C.c_uint32), ("skipped_triangles", C.c_uint32)]
 
 
 class Buoyancy(C.Structure):
@@ -127,6 +138,7 @@ SYMBOLS = {
     "fx_enforce_obstacles": (C.c_int, [_vp, _vp]),
     "fx_set_obstacle_bodies": (C.c_int, [_vp, C.POINTER(ObstacleBody), C.c_uint32]),
     "fx_get_obstacle_bodies": (C.c_int, [_vp, C.POINTER(ObstacleBody), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fx_set_obstacle_meshes": (C.c_int, [_vp, _vp, C.POINTER(ObstacleMesh), C.c_uint32, C.POINTER(MeshReport)]),
     "fx_set_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy)]),
     "fx_get_buoyancy": (C.c_int, [_vp, C.POINTER(Buoyancy), C.POINTER(C.c_int)]),
     "fx_set_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32]),

@@ -158,6 +158,24 @@ public:
 		out.resize(m_status == FX_OK ? n : 0);
 		return m_status == FX_OK;
 	}
+	// the mask from closed triangle meshes, voxelised on the device (fx_set_obstacle_meshes): the union of the meshes' solid sets replaces
+	// the previous mask as SetObstacles would; a rigidly moving object is a new call with a new transform.  report may be null
+	bool SetObstacleMeshes(const fx_obstacle_mesh* meshes, uint32_t count, fx_mesh_report* report = nullptr, void* stream = nullptr)
+	{
+		m_status = fx_set_obstacle_meshes(m_ctx, stream, meshes, count, report);
+		return m_status == FX_OK;
+	}
+	// one host mesh: positions float[n][3] in texture space, indices uint32[m][3], transform float[12] (row-major 3 x 4) or null
+	bool SetObstacleMesh(const std::vector<float>& positions, const std::vector<uint32_t>& indices, const float* transform = nullptr,
+		fx_mesh_report* report = nullptr, void* stream = nullptr)
+	{
+		fx_obstacle_mesh m = {};
+		m.struct_size = (uint32_t)sizeof m;
+		m.positions = positions.data(); m.indices = indices.data();
+		m.vertex_count = (uint32_t)(positions.size() / 3); m.triangle_count = (uint32_t)(indices.size() / 3);
+		m.transform = transform;
+		return SetObstacleMeshes(&m, 1, report, stream);
+	}
 
 	// not in the reference (its box is closed): the faces through which the smoke leaves (fx_set_open_walls; FX_WALL_* bits, 0 = all closed,
 	// the default) and the inflow stage alone (fx_open_inflow), directly behind the advection, beside Emit

@@ -8,6 +8,7 @@
 #include "fx_host.h"
 #include <cstring>
 #include "fx_hostmath.h"
+#include "fx_mesh_args.h"
 
 using namespace fx;
 using namespace fxh;
@@ -463,6 +464,23 @@ int fx_set_impulse(fx_ctx* ctx, int enabled)
 int fx_emit(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, emit_phase); }
 
 // ---- solid obstacles (fx_obstacle.hip) ------------------------------------------------------------------
+// the tail the two mask setters share: the 0 / 1 bytes at `src` (device memory) become the code volume in obst_spare, the count and the box come
+// back, and the new volume takes the place of the one in force.  obst_spare and obst_stats are allocated; blocks until `src` has been read
+static int install_obstacle_mask(fx_ctx* ctx, const uint8_t* src, hipStream_t s)
+{
+	FX_HIP(launch_obstacle_codes(ctx->g, src, ctx->obst_spare, ctx->obst_stats, s));
+	unsigned st[8];
+	FX_HIP(hipMemcpyAsync(st, ctx->obst_stats, sizeof st, hipMemcpyDeviceToHost, s));
+	FX_HIP(hipStreamSynchronize(s));                                        // the count and the box size the enforce launch; `solid` is free again
+	std::swap(ctx->obst_code, ctx->obst_spare);
+	ctx->obst_cells = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
+	for (int a = 0; a < 3; ++a) {
+		ctx->obst_lo[a] = ctx->obst_cells ? (int)st[2 + a] : 0;
+		ctx->obst_hi[a] = ctx->obst_cells ? (int)st[5 + a] + 1 : 0;
+	}
+	return FX_OK;
+}
+
 int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t bytes, uint32_t flags)
 {
 	if (const int rc = sim_guard(ctx)) return rc;
@@ -492,17 +510,7 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 		FX_HIP(hipMemcpyAsync(ctx->stage, solid, n, hipMemcpyHostToDevice, s));
 		src = reinterpret_cast<const uint8_t*>(ctx->stage);
 	}
-	FX_HIP(launch_obstacle_codes(ctx->g, src, ctx->obst_spare, ctx->obst_stats, s));
-	unsigned st[8];
-	FX_HIP(hipMemcpyAsync(st, ctx->obst_stats, sizeof st, hipMemcpyDeviceToHost, s));
-	FX_HIP(hipStreamSynchronize(s));                                        // the count and the box size the enforce launch; `solid` is free again
-	std::swap(ctx->obst_code, ctx->obst_spare);
-	ctx->obst_cells = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
-	for (int a = 0; a < 3; ++a) {
-		ctx->obst_lo[a] = ctx->obst_cells ? (int)st[2 + a] : 0;
-		ctx->obst_hi[a] = ctx->obst_cells ? (int)st[5 + a] + 1 : 0;
-	}
-	return FX_OK;
+	return install_obstacle_mask(ctx, src, s);
 }
 
 int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* solid_cells)
@@ -550,6 +558,65 @@ int fx_get_obstacle_bodies(fx_ctx* ctx, fx_obstacle_body* out, uint32_t capacity
 	if (!count || (capacity && !out)) return FX_E_INVALID;
 	*count = (uint32_t)ctx->obst_bodies.size();
 	for (uint32_t k = 0; k < capacity && k < *count; ++k) out[k] = ctx->obst_bodies[k];
+	return FX_OK;
+}
+
+// ---- the mask from triangle meshes (fx_voxelize.hip): scatter and fill per mesh into the staging buffer, then fx_set_obstacles' own tail --------
+int fx_set_obstacle_meshes(fx_ctx* ctx, void* stream, const fx_obstacle_mesh* meshes, uint32_t count, fx_mesh_report* report)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (const int rc = mesh_args_status(meshes, count)) return rc;
+	if (ctx->g.Zg <= 1) return FX_E_INVALID;                                // a 2-D grid has no columns to fill
+	if (ctx->desc.jacobi_mode == FX_JACOBI_FAITHFUL) return FX_E_INVALID;  // as fx_set_obstacles
+	if (ctx->solver.kind == FX_PRESSURE_MULTIGRID) return FX_E_STATE;
+	DeviceGuard dg(ctx->device);
+	const Geom& g = ctx->g;
+	const size_t n = g.plane() * (size_t)g.Zg;
+	hipStream_t s = pick_stream(ctx, stream);
+	// everything is allocated before anything is enqueued: the mask in force stays in force if one of these fails
+	if (!ctx->obst_spare && hipMalloc((void**)&ctx->obst_spare, n) != hipSuccess) { (void)hipGetLastError(); ctx->obst_spare = nullptr; return FX_E_NOMEM; }
+	if (!ctx->obst_stats && hipMalloc((void**)&ctx->obst_stats, 8 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->obst_stats = nullptr; return FX_E_NOMEM; }
+	if (!ctx->vox_report && hipMalloc((void**)&ctx->vox_report, kVoxReportWords * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->vox_report = nullptr; return FX_E_NOMEM; }
+	if (!ctx->vox_bits) {
+		const size_t bytes = (size_t)g.Y * g.Zg * voxel_row_words(g) * sizeof(unsigned);
+		if (hipMalloc((void**)&ctx->vox_bits, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->vox_bits = nullptr; return FX_E_NOMEM; }
+		FX_HIP(hipMemsetAsync(ctx->vox_bits, 0, bytes, s));                 // once: the fill kernel leaves it all zero
+	}
+	const size_t work = mesh_work_bytes(meshes, count);
+	if (ctx->vox_work_bytes < work) {
+		if (ctx->vox_work) { FX_HIP(hipFree(ctx->vox_work)); ctx->vox_work = nullptr; ctx->vox_work_bytes = 0; }
+		if (hipMalloc(&ctx->vox_work, work) != hipSuccess) { (void)hipGetLastError(); ctx->vox_work = nullptr; return FX_E_NOMEM; }
+		ctx->vox_work_bytes = work;
+	}
+	if (const int rc = ensure_stage(ctx, n)) return rc;
+	uint8_t* mask = reinterpret_cast<uint8_t*>(ctx->stage);
+	FX_HIP(hipMemsetAsync(ctx->vox_report, 0, kVoxReportWords * sizeof(unsigned), s));
+	for (uint32_t k = 0; k < count; ++k) {
+		const fx_obstacle_mesh& m = meshes[k];
+		VoxMesh vm = { m.positions, m.indices, m.transform, m.vertex_count, m.triangle_count };
+		if (m.triangle_count && !(m.flags & FX_MESH_DEVICE)) {               // a host mesh: its copy lies behind the list of large triangles
+			char* at = static_cast<char*>(ctx->vox_work) + (size_t)16 * m.triangle_count;
+			const size_t ib = (size_t)12 * m.triangle_count, pb = (size_t)12 * m.vertex_count;
+			FX_HIP(hipMemcpyAsync(at, m.indices, ib, hipMemcpyHostToDevice, s));
+			vm.idx = reinterpret_cast<const uint32_t*>(at);
+			if (pb) FX_HIP(hipMemcpyAsync(at + ib, m.positions, pb, hipMemcpyHostToDevice, s));
+			vm.pos = reinterpret_cast<const float*>(at + ib);
+			if (m.transform) {
+				FX_HIP(hipMemcpyAsync(at + ib + pb, m.transform, 48, hipMemcpyHostToDevice, s));
+				vm.xf = reinterpret_cast<const float*>(at + ib + pb);
+			}
+		}
+		FX_HIP(launch_voxel_scatter(g, vm, ctx->vox_bits, ctx->vox_report, ctx->vox_report + 2 + k, static_cast<uint4*>(ctx->vox_work), s));
+		if (k == 0 || m.triangle_count) FX_HIP(launch_voxel_fill(g, ctx->vox_bits, mask, k == 0, ctx->vox_report, s));
+	}
+	unsigned rep[2];
+	FX_HIP(hipMemcpyAsync(rep, ctx->vox_report, sizeof rep, hipMemcpyDeviceToHost, s));
+	if (const int rc = install_obstacle_mask(ctx, mask, s)) return rc;        // (synchronises: rep is there, the meshes are free again)
+	if (report) {
+		report->solid_cells = ctx->obst_cells;
+		report->open_columns = rep[0];
+		report->skipped_triangles = rep[1];
+	}
 	return FX_OK;
 }
 

@@ -72,6 +72,11 @@ struct fx_ctx {
 	// the solids' rigid-body velocities (fx_set_obstacle_bodies; configuration on the same terms): a solid cell belongs to the first body whose
 	// box holds its centre.  In force while obst_code is set and the list is not empty: the moving kernels (fx_obstacle_moving.hip) then run
 	std::vector<fx_obstacle_body> obst_bodies;   // may be set with no mask in force; empty = every solid rests (default)
+	// the mesh voxeliser's scratch (fx_set_obstacle_meshes, fx_voxelize.hip), allocated by the first call: nothing in it outlives a call
+	unsigned* vox_bits = nullptr;   // the toggle bitmap, [Z][Y][X / 32 + 1] words; all zero between calls (the fill kernel clears what it reads)
+	unsigned* vox_report = nullptr; // device, fx::kVoxReportWords words: open columns, skipped triangles, then per mesh the length of its list of large triangles
+	void* vox_work = nullptr;       // the list of large triangles (16 bytes a triangle), behind it the staged copy of a host mesh
+	size_t vox_work_bytes = 0;
 	// open walls (fx_set_open_walls; configuration on the same terms): FX_WALL_* bits, 0 = all six faces closed: every launch is today's
 	uint32_t open_faces = 0;
 	// buoyancy (fx_set_buoyancy / fx_set_heat_sources; configuration on the same terms): the temperature ping-pong pair, fp32 whatever the storage,

@@ -191,6 +191,17 @@ hipError_t launch_divergence_obs_mov(const Geom& g, int half_store, const void* 
 	float* b, int z_begin, int z_end, hipStream_t s);
 hipError_t launch_project_bnd_mov(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
 	const fx_obstacle_body* list, int count, void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
+// ---- the mesh voxeliser (fx_voxelize.hip; fx_set_obstacle_meshes), whole 3-D grids only: closed triangle meshes -> the 0 / 1 byte mask
+// launch_obstacle_codes reads.  The rule is integer arithmetic on coordinates quantised to 1 / 256 of a cell (include/fluidx_hip.h).
+// VoxMesh: one mesh, every pointer device memory; xf null = no transform.  bits: the toggle bitmap, [Z][Y][voxel_row_words] words, all zero on
+// entry to the scatter and again behind the fill.  report: word 0 open columns, word 1 skipped triangles (both added to).  nbig / list: a
+// zeroed word and room for nt entries -- the triangles whose clipped (y, z) box is too large for one wave go through them.
+struct VoxMesh { const float* pos; const uint32_t* idx; const float* xf; uint32_t nv, nt; };
+enum { kVoxReportWords = 2 + FX_MAX_OBSTACLE_MESHES };
+inline int voxel_row_words(const Geom& g) { return g.X / 32 + 1; }                   // bit X: the virtual cell beyond the +x wall
+hipError_t launch_voxel_scatter(const Geom& g, const VoxMesh& m, unsigned* bits, unsigned* report, unsigned* nbig, uint4* list, hipStream_t s);
+// the prefix XOR along x of one mesh's toggles, written (first) or ORed into mask[Z][Y][X]; clears the bitmap
+hipError_t launch_voxel_fill(const Geom& g, unsigned* bits, uint8_t* mask, bool first, unsigned* report, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

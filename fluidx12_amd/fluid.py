@@ -357,6 +357,46 @@ class Fluid:
             arr[k].pivot = (C.c_float * 3)(*[float(v) for v in b.get("pivot", [0.5 * (l + h) for l, h in zip(lo, hi)])])
         capi.check(self._lib.fx_set_obstacle_bodies(self._ctx, arr if items else None, len(items)), "SetObstacleBodies")
 
+    def SetObstacleMeshes(self, meshes, stream=None):
+        """the obstacle mask from closed triangle meshes, voxelised on the device (fx_set_obstacle_meshes): a sequence of
+        (positions, indices, transform or None) -- positions (n, 3) float32 in texture space, indices (m, 3) uint32, transform 12 floats
+        (row-major 3 x 4) -- as anything numpy takes as an array, or, all three of a mesh, as torch tensors on the context's device (float32 /
+        int32 or uint32 / float32), which are read in place.  The mask is the union of the meshes' solid sets and replaces the previous mask as
+        SetObstacles would; a rigidly moving object is a new call with a new transform.  -> {"solid_cells", "open_columns" (0 for watertight
+        meshes), "skipped_triangles" (an index out of range, a non-finite position)}.  Whole-grid, fixed-mode 3-D contexts only."""
+        self._need()
+        items = list(meshes)
+        arr = (capi.ObstacleMesh * max(len(items), 1))()
+        keep = []                                                       # the arrays behind the pointers, alive until the call returns
+        for k, (pos, idx, xf) in enumerate(items):
+            arr[k].struct_size = C.sizeof(capi.ObstacleMesh)
+            if hasattr(pos, "data_ptr") and getattr(pos, "is_cuda", False):
+                import torch
+                p = pos.to(torch.float32).contiguous().reshape(-1, 3)
+                if idx.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not idx.is_cuda:
+                    raise TypeError("SetObstacleMeshes: a device mesh takes its indices as an int32 or uint32 tensor on the same device")
+                i = idx.contiguous().reshape(-1, 3)
+                x = None if xf is None else xf.to(torch.float32).contiguous().reshape(12)
+                if x is not None and not x.is_cuda:
+                    raise TypeError("SetObstacleMeshes: a device mesh takes its transform as a tensor on the same device")
+                keep.append((p, i, x))
+                arr[k].flags = capi.MESH_DEVICE
+                arr[k].positions, arr[k].indices = p.data_ptr() or None, i.data_ptr() or None
+                arr[k].vertex_count, arr[k].triangle_count = p.shape[0], i.shape[0]
+                arr[k].transform = None if x is None else x.data_ptr()
+                continue
+            p = np.ascontiguousarray(np.asarray(pos, np.float32).reshape(-1, 3))
+            i = np.ascontiguousarray(np.asarray(idx).astype(np.uint32, copy=False).reshape(-1, 3))
+            x = None if xf is None else np.ascontiguousarray(np.asarray(xf, np.float32).reshape(12))
+            keep.append((p, i, x))
+            arr[k].flags = 0
+            arr[k].positions, arr[k].indices = (p.ctypes.data if p.size else None), (i.ctypes.data if i.size else None)
+            arr[k].vertex_count, arr[k].triangle_count = p.shape[0], i.shape[0]
+            arr[k].transform = None if x is None else x.ctypes.data
+        rep = capi.MeshReport()
+        capi.check(self._lib.fx_set_obstacle_meshes(self._ctx, stream, arr if items else None, len(items), C.byref(rep)), "SetObstacleMeshes")
+        return {"solid_cells": int(rep.solid_cells), "open_columns": int(rep.open_columns), "skipped_triangles": int(rep.skipped_triangles)}
+
     def GetObstacleBodies(self):
         """the list in force (fx_get_obstacle_bodies), as dicts with the keys SetObstacleBodies takes"""
         self._need()

@@ -395,7 +395,8 @@ int fx_enforce_obstacles(fx_ctx* ctx, void* stream);
  * kept across fx_update_frame, not checkpointed, not part of fx_field_digest.  count 0 (list may be NULL) is the default, "every solid
  * rests": every call then runs exactly the launches it runs without this function.  The list may be set with or without a mask in force and
  * takes effect once one is (as heat sources wait for buoyancy); it does not depend on the order of the two calls.  A cell inside several
- * boxes belongs to the first body in list order.  The library neither moves nor rasterises the mask, and no force acts on the body.
+ * boxes belongs to the first body in list order.  The library does not move the mask (fx_set_obstacle_meshes below rasterises it from meshes,
+ * where the caller's transform says), and no force acts on the body.
  * fx_set_obstacle_bodies: FX_E_INVALID, the previous list staying in force, for count > FX_MAX_OBSTACLE_BODIES, count with a NULL list, a wrong
  * struct_size, non-zero flags, a non-finite member, box_lo[a] > box_hi[a], a context that owns fewer planes than the grid (slab ranks of every
  * transport) and FX_JACOBI_FAITHFUL contexts (fx_set_obstacles refuses them too); FX_E_STATE for FX_FLAG_RENDER_ONLY.
@@ -410,6 +411,55 @@ typedef struct fx_obstacle_body {
 } fx_obstacle_body;
 int fx_set_obstacle_bodies(fx_ctx* ctx, const fx_obstacle_body* list, uint32_t count);
 int fx_get_obstacle_bodies(fx_ctx* ctx, fx_obstacle_body* out, uint32_t capacity, uint32_t* count);
+
+/* The mask from triangle meshes: a solid voxeliser on the device (fx_voxelize.hip).  fx_set_obstacle_meshes voxelises up to
+ * FX_MAX_OBSTACLE_MESHES closed triangle meshes into solid sets, ORs them into one mask and installs it exactly as
+ * fx_set_obstacles(ctx, stream, mask, X * Y * Z, FX_OBSTACLES_DEVICE) would: the same code volume, count and bounding box, the same "returns
+ * once the inputs have been read" (it blocks like fx_set_obstacles), the same configuration terms.  fx_get_obstacles then returns the
+ * voxelised mask, fx_set_obstacles(NULL) detaches it, fx_set_obstacle_bodies acts on it unchanged.  A rigidly animated object costs its
+ * 48-byte transform per frame: with FX_MESH_DEVICE the positions and indices stay where they are.
+ * The rule is exact integer arithmetic behind one rounding per coordinate (tests/voxelize_ref.py restates it in numpy).  With N = (X, Y, Z),
+ * per position v and axis a:
+ *   1 transform   with a transform m: p_a = ((m[4a] * v_x + m[4a+1] * v_y) + m[4a+2] * v_z) + m[4a+3], every multiply and add rounded to fp32
+ *                 on its own (no fused multiply-add); without one p_a = v_a, bits untouched
+ *   2 quantise    to 1 / 256 of a cell: t = p_a * (float)(256 * N_a) rounded to fp32, clamped to [-262144, 262144]; q_a = (int)rintf(t)
+ *                 (ties to even).  Cell i's centre is 256 i + 128.  A triangle is SKIPPED (skipped_triangles += 1) if one of its indices is
+ *                 >= vertex_count or a transformed coordinate p_a of one of its vertices is not finite
+ *   3 triangle    (a, b, c) quantised, int64 from here: A = (b_y - a_y)(c_z - a_z) - (b_z - a_z)(c_y - a_y).  A = 0: the triangle is edge-on,
+ *                 covers no column and contributes nothing (this is not "skipped").  A < 0: swap b and c and negate A
+ *   4 column      (j, k) with P = (256 j + 128, 256 k + 128) is COVERED iff for each directed edge p -> r of a -> b, b -> c, c -> a, with
+ *                 dy = r_y - p_y, dz = r_z - p_z, E = dy (P_z - p_z) - dz (P_y - p_y):  E > 0, or E == 0 and (dy > 0 or (dy == 0 and dz > 0)).
+ *                 The tie rule is the sample shifted by (-eps^2, +eps): a shared edge or vertex counts exactly once, whatever the triangle
+ *                 order or winding
+ *   5 toggle      with e1 = b - a, e2 = c - a: n_y = e1_z e2_x - e1_x e2_z, n_z = e1_x e2_y - e1_y e2_x,
+ *                 T = (a_x - 128) A - (n_y (P_y - a_y) + n_z (P_z - a_z)), i0 = clamp(ceil(T / (256 A)), 0, X) with the ceiling of the exact
+ *                 quotient.  The triangle toggles covered column (j, k) at i0; index X is a virtual cell beyond the +x wall
+ *   6 fill        per mesh, solid(i, j, k) = XOR over t <= i of toggles(t, j, k), for i < X.  open_columns counts, summed over the meshes,
+ *                 the columns whose number of toggles INCLUDING index X is odd: 0 for a watertight mesh wherever it lies, also across a wall
+ *   7 union       mask = OR over the meshes; solid_cells = what fx_set_obstacles counts
+ * The result does not depend on the order of the triangles, of the vertices within one, or on the winding.  Bad geometry is never an error
+ * (device meshes cannot be looked at up front): it is defined by the rule and counted in the report.  Magnitudes: |q| <= 2^18, |A|, |n| < 2^40,
+ * |T| < 2^61.
+ * positions: texture space, cell (x, y, z)'s centre = ((x + .5) / X, (y + .5) / Y, (z + .5) / Z).  A mesh with triangle_count == 0 is legal
+ * and contributes nothing (positions and indices may then be NULL); meshes that leave every cell empty install an all-zero mask, which keeps
+ * the obstacle kernels in force.  flags & FX_MESH_DEVICE: positions, indices and transform are device memory of the context's device, read
+ * by work enqueued on `stream` during this call only; otherwise host memory.  report may be NULL.
+ * FX_E_INVALID, the previous mask staying in force, for count == 0 (detaching stays fx_set_obstacles(NULL)) or > FX_MAX_OBSTACLE_MESHES, a
+ * NULL list, a wrong struct_size, unknown flag bits, NULL positions or indices with triangle_count > 0, 2-D grids, and the contexts
+ * fx_set_obstacles refuses (slab ranks, FX_JACOBI_FAITHFUL); FX_E_STATE for FX_FLAG_RENDER_ONLY and while the multigrid solver is selected;
+ * FX_E_NOMEM if the code volume or the voxeliser's scratch (a bitmap of X / 32 + 1 words per row, 16 bytes per triangle, a host mesh's copy)
+ * cannot be allocated.  The scratch is allocated by the first call and freed with the context. */
+#define FX_MAX_OBSTACLE_MESHES 16u
+#define FX_MESH_DEVICE 0x1u          /* positions / indices / transform are device memory of the context's device */
+typedef struct fx_obstacle_mesh {
+	uint32_t struct_size, flags;     /* sizeof(fx_obstacle_mesh); FX_MESH_DEVICE or 0 */
+	const float* positions;          /* float[vertex_count][3], texture space */
+	const uint32_t* indices;         /* uint32[triangle_count][3] */
+	uint32_t vertex_count, triangle_count;
+	const float* transform;          /* float[12], row-major 3x4 applied to every position; NULL = none */
+} fx_obstacle_mesh;
+typedef struct fx_mesh_report { uint64_t solid_cells; uint32_t open_columns, skipped_triangles; } fx_mesh_report;
+int fx_set_obstacle_meshes(fx_ctx* ctx, void* stream, const fx_obstacle_mesh* meshes, uint32_t count, fx_mesh_report* report);
 
 /* Open walls (no reference counterpart: the reference's box is closed on all six faces -- the clamped neighbour indices of its stages and the
  * wall damping of its projection).  fx_set_open_walls names the faces through which the smoke may leave; the step is then
