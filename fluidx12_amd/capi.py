@@ -36,6 +36,9 @@ ADVECT_SEMI_LAGRANGIAN, ADVECT_MACCORMACK = 0, 1   # FX_ADVECT_*: fx_set_advecti
 PRESSURE_JACOBI, PRESSURE_MULTIGRID = 0, 1         # FX_PRESSURE_*: fx_set_pressure_solver
 MG_NO_TAIL = 0x1                                   # FX_MG_NO_TAIL
 MG_MAX_LEVELS = 12                                 # FX_MG_MAX_LEVELS
+MAX_PARTICLES = 1 << 26                            # FX_MAX_PARTICLES
+PARTICLES_DEVICE = 0x1                             # FX_PARTICLES_DEVICE: fx_set_particles / fx_sample_velocity take device pointers
+PARTICLE_EULER, PARTICLE_MIDPOINT = 0, 1           # FX_PARTICLE_*: fx_particle_params.scheme
 
 
 class Desc(C.Structure):
@@ -88,6 +91,10 @@ class HeatSource(C.Structure):
 class PressureSolver(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("cycles", C.c_uint32), ("pre_sweeps", C.c_uint32), ("post_sweeps", C.c_uint32),
                 ("coarse_sweeps", C.c_uint32), ("max_levels", C.c_uint32), ("omega", C.c_float)]
+
+
+class ParticleParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("scheme", C.c_uint32), ("drift", C.c_float * 3), ("lifetime", C.c_float)]
 
 
 class Timing(C.Structure):
@@ -144,6 +151,13 @@ SYMBOLS = {
     "fx_set_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32]),
     "fx_get_heat_sources": (C.c_int, [_vp, C.POINTER(HeatSource), C.c_uint32, C.POINTER(C.c_uint32)]),
     "fx_heat": (C.c_int, [_vp, _vp]),
+    "fx_set_particles": (C.c_int, [_vp, _vp, _fp, C.c_uint32, C.c_uint32]),
+    "fx_get_particles": (C.c_int, [_vp, _fp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fx_particles_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "fx_set_particle_params": (C.c_int, [_vp, C.POINTER(ParticleParams)]),
+    "fx_get_particle_params": (C.c_int, [_vp, C.POINTER(ParticleParams)]),
+    "fx_move_particles": (C.c_int, [_vp, _vp]),
+    "fx_sample_velocity": (C.c_int, [_vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),

@@ -183,6 +183,40 @@ public:
 	bool GetOpenWalls(uint32_t& faces) { m_status = fx_get_open_walls(m_ctx, &faces); return m_status == FX_OK; }
 	bool OpenInflow(void* stream = nullptr) { m_status = fx_open_inflow(m_ctx, stream); return m_status == FX_OK; }
 
+	// not in the reference (it carries nothing but its grid fields): tracer particles that ride the flow -- records float[4] = (x, y, z, age) in
+	// texture space, age >= 0 alive (fx_set_particles; count 0 frees the set, the default) --, moved by Simulate behind the projection; the
+	// context's own buffer for zero-copy drawing (fx_particles_device), how they move (fx_set_particle_params; nullptr = the defaults), the
+	// stage alone (fx_move_particles) and the velocity at points (fx_sample_velocity: points float[n][4], out float[n][3])
+	bool SetParticles(const float* records, uint32_t count, void* stream = nullptr, bool deviceMemory = false)
+	{
+		m_status = fx_set_particles(m_ctx, stream, records, count, deviceMemory ? FX_PARTICLES_DEVICE : 0u);
+		return m_status == FX_OK;
+	}
+	bool SetParticles(const std::vector<float>& records) { return SetParticles(records.data(), (uint32_t)(records.size() / 4)); }
+	bool GetParticles(std::vector<float>& out)
+	{
+		uint32_t n = 0;
+		if ((m_status = fx_get_particles(m_ctx, nullptr, 0, &n)) != FX_OK) { out.clear(); return false; }
+		out.resize((size_t)n * 4);
+		m_status = fx_get_particles(m_ctx, out.data(), n, &n);
+		out.resize(m_status == FX_OK ? (size_t)n * 4 : 0);
+		return m_status == FX_OK;
+	}
+	bool ParticlesDevice(void*& records, uint32_t& count) { m_status = fx_particles_device(m_ctx, &records, &count); return m_status == FX_OK; }
+	bool SetParticleParams(const fx_particle_params* params) { m_status = fx_set_particle_params(m_ctx, params); return m_status == FX_OK; }
+	bool SetParticleParams(uint32_t scheme, float driftX = 0.0f, float driftY = 0.0f, float driftZ = 0.0f, float lifetime = 0.0f)
+	{
+		const fx_particle_params p = { (uint32_t)sizeof(fx_particle_params), 0u, scheme, { driftX, driftY, driftZ }, lifetime };
+		return SetParticleParams(&p);
+	}
+	bool GetParticleParams(fx_particle_params& out) { m_status = fx_get_particle_params(m_ctx, &out); return m_status == FX_OK; }
+	bool MoveParticles(void* stream = nullptr) { m_status = fx_move_particles(m_ctx, stream); return m_status == FX_OK; }
+	bool SampleVelocity(const float* points, uint32_t count, float* out, void* stream = nullptr, bool deviceMemory = false)
+	{
+		m_status = fx_sample_velocity(m_ctx, stream, points, count, out, deviceMemory ? FX_PARTICLES_DEVICE : 0u);
+		return m_status == FX_OK;
+	}
+
 	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
 	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }

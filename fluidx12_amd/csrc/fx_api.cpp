@@ -718,6 +718,99 @@ int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uin
 
 int fx_heat(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, heat_phase); }
 
+// ---- tracer particles and the point query (fx_particles.hip) ---------------------------------------------------
+// The set lives in a buffer of its own that only this call allocates and frees: the new one is filled beside the one in force, which stays in
+// force if anything fails.  Blocks until the caller's records have been read.
+int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t count, uint32_t flags)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (flags & ~(uint32_t)FX_PARTICLES_DEVICE) return FX_E_INVALID;
+	if (count > FX_MAX_PARTICLES || (count && !records)) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	float* fresh = nullptr;
+	if (count) {
+		const size_t bytes = (size_t)count * 16;
+		if (hipMalloc((void**)&fresh, bytes) != hipSuccess) { (void)hipGetLastError(); return FX_E_NOMEM; }
+		hipStream_t s = pick_stream(ctx, stream);
+		hipError_t e = hipMemcpyAsync(fresh, records, bytes, (flags & FX_PARTICLES_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+		if (e == hipSuccess) e = hipStreamSynchronize(s);
+		if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(fresh); ctx->last_error = std::string("fx_set_particles: ") + hipGetErrorString(e); return FX_E_DEVICE; }
+	}
+	if (ctx->part) FX_HIP(hipFree(ctx->part));                              // (hipFree waits for the device: nothing moves the old set any more)
+	ctx->part = fresh;
+	ctx->part_count = count;
+	return FX_OK;
+}
+
+int fx_get_particles(fx_ctx* ctx, float* out, uint32_t capacity, uint32_t* count)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;             // (slab ranks may ask: the set is empty there)
+	if (!count || (capacity && !out)) return FX_E_INVALID;
+	*count = ctx->part_count;
+	const uint32_t n = std::min(capacity, ctx->part_count);
+	if (!n) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	FX_HIP(hipDeviceSynchronize());
+	FX_HIP(hipMemcpy(out, ctx->part, (size_t)n * 16, hipMemcpyDeviceToHost));
+	return FX_OK;
+}
+
+int fx_particles_device(fx_ctx* ctx, void** records, uint32_t* count)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (records) *records = ctx->part;
+	if (count) *count = ctx->part_count;
+	return FX_OK;
+}
+
+int fx_set_particle_params(fx_ctx* ctx, const fx_particle_params* p)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	const fx_particle_params def = { (uint32_t)sizeof(fx_particle_params), 0u, FX_PARTICLE_MIDPOINT, { 0.0f, 0.0f, 0.0f }, 0.0f };
+	if (!p) { ctx->part_prm = def; return FX_OK; }
+	if (p->struct_size != sizeof(fx_particle_params) || p->flags != 0) return FX_E_INVALID;
+	if (p->scheme != FX_PARTICLE_EULER && p->scheme != FX_PARTICLE_MIDPOINT) return FX_E_INVALID;
+	for (int a = 0; a < 3; ++a) if (!std::isfinite(p->drift[a])) return FX_E_INVALID;
+	if (!std::isfinite(p->lifetime) || p->lifetime < 0.0f) return FX_E_INVALID;
+	ctx->part_prm = *p;
+	return FX_OK;
+}
+
+int fx_get_particle_params(fx_ctx* ctx, fx_particle_params* out)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!out) return FX_E_INVALID;
+	*out = ctx->part_prm;
+	return FX_OK;
+}
+
+int fx_move_particles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, particles_phase); }
+
+int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t count, float* out, uint32_t flags)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (flags & ~(uint32_t)FX_PARTICLES_DEVICE) return FX_E_INVALID;
+	if (count > FX_MAX_PARTICLES) return FX_E_INVALID;
+	if (count == 0) return FX_OK;
+	if (!points || !out) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	hipStream_t s = pick_stream(ctx, stream);
+	if (flags & FX_PARTICLES_DEVICE) {                                      // enqueue only: the kernel loads a point as one 16-byte vector
+		if (((uintptr_t)points & 15u) || ((uintptr_t)out & 3u)) return FX_E_INVALID;
+		FX_HIP(launch_sample_velocity(ctx->g, ctx->half, ctx->vel[0], points, out, count, s));
+		return FX_OK;
+	}
+	const size_t in_bytes = (size_t)count * 16, out_bytes = (size_t)count * 12;
+	if (const int rc = ensure_stage(ctx, in_bytes + out_bytes)) return rc;
+	float* pts = ctx->stage;
+	float* res = ctx->stage + (size_t)count * 4;
+	FX_HIP(hipMemcpyAsync(pts, points, in_bytes, hipMemcpyHostToDevice, s));
+	FX_HIP(launch_sample_velocity(ctx->g, ctx->half, ctx->vel[0], pts, res, count, s));
+	FX_HIP(hipMemcpyAsync(out, res, out_bytes, hipMemcpyDeviceToHost, s));
+	FX_HIP(hipStreamSynchronize(s));
+	return FX_OK;
+}
+
 // ---- the advection scheme (fx_maccormack.hip) ---------------------------------------------------------------
 int fx_set_advection_scheme(fx_ctx* ctx, uint32_t scheme)
 {

@@ -101,6 +101,11 @@ struct fx_ctx {
 	float* mg_e[fx::kMgMaxLevels][2] = {};
 	float* mg_b[fx::kMgMaxLevels] = {};
 	int mg_cur[fx::kMgMaxLevels] = {};
+	// tracer particles (fx_set_particles / fx_set_particle_params; caller data on the same terms): count records (x, y, z, age) of 16 bytes,
+	// allocated and freed by fx_set_particles alone (fx_particles.hip: k_move_particles moves them in place behind the projection)
+	float* part = nullptr;          // device; null = no set: every call is the one it is without particles
+	uint32_t part_count = 0;
+	fx_particle_params part_prm = { (uint32_t)sizeof(fx_particle_params), 0u, FX_PARTICLE_MIDPOINT, { 0.0f, 0.0f, 0.0f }, 0.0f };
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

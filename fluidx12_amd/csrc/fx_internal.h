@@ -202,6 +202,13 @@ inline int voxel_row_words(const Geom& g) { return g.X / 32 + 1; }              
 hipError_t launch_voxel_scatter(const Geom& g, const VoxMesh& m, unsigned* bits, unsigned* report, unsigned* nbig, uint4* list, hipStream_t s);
 // the prefix XOR along x of one mesh's toggles, written (first) or ORed into mask[Z][Y][X]; clears the bitmap
 hipError_t launch_voxel_fill(const Geom& g, unsigned* bits, uint8_t* mask, bool first, unsigned* report, hipStream_t s);
+// ---- tracer particles and the point query (fx_particles.hip; fx_set_particles, fx_sample_velocity), whole grids only (hipErrorNotSupported for a
+// slab geometry).  records: count x (x, y, z, age), device memory, 16-byte aligned, moved in place one step of dt through vel0; code: the obstacle
+// bytes or null; faces: the open walls' FX_WALL_* bits or 0.  Reads vel0 and code, writes the records: no field of the simulation is touched
+hipError_t launch_move_particles(const Geom& g, int half_store, const fx_particle_params& prm, const void* vel0, const uint8_t* code, unsigned faces,
+	float dt, float* records, uint32_t count, hipStream_t s);
+// points: count x float4 (w ignored), out: count x 3 floats, both device memory; out = the stored velocity vel0 sampled as the particles sample it
+hipError_t launch_sample_velocity(const Geom& g, int half_store, const void* vel0, const float* points, float* out, uint32_t count, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

@@ -807,6 +807,19 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// Tracer particles (fx_particles.hip): behind the projection, every live record takes one step through velocity[0], the field the projection has
+// just written.  One launch over the records, in place; it reads the velocity, the obstacle code and the open-wall bits and writes the particle
+// buffer alone, so no field of the step knows of it.  Nothing is allocated, copied or waited for here (fx_set_particles did all of that).  Booked
+// with the projection: fx_timing has no mark of its own for it.
+int particles_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->part || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_PROJECT);
+	FX_HIP(launch_move_particles(ctx->g, ctx->half, ctx->part_prm, ctx->vel[0], ctx->obst_code, ctx->open_faces, ctx->time_step, ctx->part, ctx->part_count, s));
+	return FX_OK;
+}
+
 // The optional stages between the advection and the divergence, each a no-op unless its feature is set (whole-grid contexts only: the setters
 // refuse slab ranks).  The order is the contract, every phase's own comment gives its half of it: the inflow pass scales what the advection
 // sampled, before the emitters add to it; buoyancy reads the alpha the emitters added; the enforce pass clears the solid cells of everything
@@ -839,6 +852,7 @@ int simulate_impl(fx_ctx* ctx, hipStream_t s)
 		ctx->fz_fuse_div = false;                      // (consumed by the dense sweep; never left standing for a later stage call)
 		if (rc) return rc;
 		for (fx_ctx* m : M) if ((rc = project_phase(m, CS(m, s)))) return rc;
+		for (fx_ctx* m : M) if ((rc = particles_phase(m, CS(m, s)))) return rc;    // (one null test per member while no set exists)
 	} else {
 		for (fx_ctx* m : M) {
 			DeviceGuard dg(m->device);

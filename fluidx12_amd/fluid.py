@@ -549,6 +549,90 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_heat(self._ctx, stream), "Heat")
 
+    def SetParticles(self, records, stream=None):
+        """tracer particles carried by the flow (fx_set_particles): `records` is anything numpy takes as an array of shape (n, 4) = (x, y, z, age)
+        -- positions in texture space [0, 1]^3, age >= 0 alive, anything else dead -- or a float32 torch tensor of that shape on the context's
+        device, which is copied on the device.  Replaces the set; None or an empty array frees it (default).  Simulate then moves the live
+        records behind the projection.  Caller data: kept across UpdateFrame, not stored in checkpoints.  Whole-grid contexts only."""
+        self._need()
+        if records is None:
+            capi.check(self._lib.fx_set_particles(self._ctx, stream, None, 0, 0), "SetParticles")
+            return
+        if hasattr(records, "data_ptr") and getattr(records, "is_cuda", False):
+            import torch
+            t = records.to(dtype=torch.float32).contiguous().reshape(-1, 4)
+            torch.cuda.current_stream(t.device).synchronize()      # the tensor was made on torch's stream, the library reads it on its own
+            capi.check(self._lib.fx_set_particles(self._ctx, stream, C.cast(t.data_ptr() or None, C.POINTER(C.c_float)), t.shape[0], capi.PARTICLES_DEVICE), "SetParticles")
+            return
+        r = np.ascontiguousarray(np.asarray(records, np.float32).reshape(-1, 4))
+        capi.check(self._lib.fx_set_particles(self._ctx, stream, _fp(r) if r.size else None, r.shape[0], 0), "SetParticles")
+
+    def GetParticles(self):
+        """the set as it stands (fx_get_particles; blocks like download): float32 (n, 4)"""
+        self._need()
+        dev, n = self.ParticlesDevice()
+        out = np.empty((n, 4), np.float32)
+        got = C.c_uint32(0)
+        capi.check(self._lib.fx_get_particles(self._ctx, _fp(out) if n else None, n, C.byref(got)), "GetParticles")
+        return out[:got.value]
+
+    def ParticlesDevice(self):
+        """(device address of the context's record buffer, count) for zero-copy drawing and respawning (fx_particles_device); (0, 0) with no
+        set.  Valid until the next SetParticles or Release"""
+        self._need()
+        p, n = C.c_void_p(None), C.c_uint32(0)
+        capi.check(self._lib.fx_particles_device(self._ctx, C.byref(p), C.byref(n)), "ParticlesDevice")
+        return int(p.value or 0), int(n.value)
+
+    def SetParticleParams(self, scheme="midpoint", drift=(0.0, 0.0, 0.0), lifetime=0.0, flags=0):
+        """how the particles move (fx_set_particle_params): scheme "midpoint" (default) or "euler" (or a capi.PARTICLE_* value), `drift` added to
+        the sampled velocity (texture space per second; settling ash: negative y), `lifetime` in seconds (0 = immortal).  SetParticleParams(None)
+        restores the defaults."""
+        self._need()
+        if scheme is None:
+            capi.check(self._lib.fx_set_particle_params(self._ctx, None), "SetParticleParams")
+            return
+        p = capi.ParticleParams()
+        p.struct_size, p.flags = C.sizeof(capi.ParticleParams), int(flags)
+        p.scheme = {"euler": capi.PARTICLE_EULER, "midpoint": capi.PARTICLE_MIDPOINT}.get(scheme, scheme)
+        p.drift = (C.c_float * 3)(*[float(v) for v in drift])
+        p.lifetime = float(lifetime)
+        capi.check(self._lib.fx_set_particle_params(self._ctx, C.byref(p)), "SetParticleParams")
+
+    def GetParticleParams(self):
+        """the setting in force (fx_get_particle_params) as a dict with SetParticleParams' keys"""
+        self._need()
+        p = capi.ParticleParams()
+        capi.check(self._lib.fx_get_particle_params(self._ctx, C.byref(p)), "GetParticleParams")
+        return {"scheme": {capi.PARTICLE_EULER: "euler", capi.PARTICLE_MIDPOINT: "midpoint"}.get(p.scheme, p.scheme), "drift": tuple(p.drift),
+                "lifetime": p.lifetime, "flags": p.flags}
+
+    def MoveParticles(self, stream=None):
+        """the particle stage alone (fx_move_particles): every live record one step through VELOCITY; Project does not include it"""
+        self._need()
+        capi.check(self._lib.fx_move_particles(self._ctx, stream), "MoveParticles")
+
+    def SampleVelocity(self, points, stream=None, out=None):
+        """the velocity at points of texture space (fx_sample_velocity): `points` (n, 3) or (n, 4) (a fourth column is ignored) as anything numpy
+        takes -> float32 (n, 3), blocking; or a float32 torch tensor (n, 4) on the context's device with `out` a float32 tensor (n, 3) there:
+        enqueued on `stream`, returns `out`."""
+        self._need()
+        if hasattr(points, "data_ptr") and getattr(points, "is_cuda", False):
+            if out is None or tuple(out.shape) != (points.shape[0], 3) or tuple(points.shape[1:]) != (4,) or not points.is_contiguous() or not out.is_contiguous():
+                raise TypeError("SampleVelocity: device points are a contiguous float32 (n, 4) tensor and take a contiguous float32 (n, 3) `out`")
+            fp = C.POINTER(C.c_float)
+            capi.check(self._lib.fx_sample_velocity(self._ctx, stream, C.cast(points.data_ptr() or None, fp), points.shape[0],
+                                                    C.cast(out.data_ptr() or None, fp), capi.PARTICLES_DEVICE), "SampleVelocity")
+            return out
+        p = np.asarray(points, np.float32)
+        p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((p.shape[0], 1), np.float32)], axis=1)
+        p = np.ascontiguousarray(p.reshape(-1, 4))
+        res = np.empty((p.shape[0], 3), np.float32)
+        capi.check(self._lib.fx_sample_velocity(self._ctx, stream, _fp(p) if p.size else None, p.shape[0], _fp(res) if p.size else None, 0), "SampleVelocity")
+        return res
+
     def Divergence(self, stream=None):
         capi.check(self._lib.fx_divergence(self._ctx, stream), "Divergence")
 

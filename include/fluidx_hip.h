@@ -564,6 +564,73 @@ int fx_set_heat_sources(fx_ctx* ctx, const fx_heat_source* list, uint32_t count)
 int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uint32_t* count);
 int fx_heat(fx_ctx* ctx, void* stream);
 
+/* Tracer particles and point queries (no reference counterpart: the reference carries nothing but its grid fields with the flow).  Embers, ash,
+ * debris: points that ride the velocity field, moved on the device by one gather kernel (fx_particles.hip), and their smaller sibling, "what
+ * is the wind at these points?" (fx_sample_velocity).  Particles are passive: the stage reads VELOCITY and the obstacle code and writes the
+ * particle buffer only; no field of the simulation changes by a bit because particles exist.
+ * A record is float[4] = (x, y, z, age).  x, y, z lie in texture space [0,1]^3, the space of fx_emitter.center: cell (i, j, k)'s centre is
+ * ((i + .5) / X, (j + .5) / Y, (k + .5) / Z).  age >= 0 is a live particle, in seconds; a record whose age is not >= 0 (negative or NaN) is
+ * DEAD: the stage leaves every bit of it alone.  The caller respawns by writing records, with fx_set_particles or through the pointer of
+ * fx_particles_device on the stream the steps run on.
+ * The rule, fp32, every operation rounded as written (tests/particle_ref.py restates it in numpy).  N = (X, Y, Z), dt = the time step of the
+ * last fx_update_frame, c(v) = fminf(fmaxf(v, 0), 1): a NaN becomes 0 (and -0 becomes +0), so no value, however wild, reaches an index
+ * computation unclamped -- that is what makes a record the caller wrote safe to read.
+ *   sampler U(p)  per axis a: s = c(p_a), t = s * N_a - 0.5, fl = floor(t), f = t - fl; the taps (int)fl and (int)fl + 1 are CLAMPED to
+ *                 [0, N_a - 1] whatever fx_desc.advect_address is (with s in [0,1] clamp and mirror address the same cells).  Each of the
+ *                 three component planes of VELOCITY is read with the advection's colour sampler, lerp(a, b, f) = fma(f, b - a, a), in
+ *                 the order x, then y, then z; fp16 storage widens each tap on load.  2-D grids: both z taps are plane 0, the z lerp runs
+ *                 on equal operands; all three components are returned
+ *   move, per live record (p, age):
+ *   1  k1 = U(p) + drift
+ *   2  FX_PARTICLE_MIDPOINT: m_a = c(fma(k1_a, 0.5 * dt, p_a)), k = U(m) + drift;   FX_PARTICLE_EULER: k = k1
+ *   3  q_a = fma(k_a, dt, p_a).  On a 2-D grid z is left alone altogether: q_z = p_z, bits kept, and rules 4 to 6 pass it by
+ *   4  open walls (fx_set_open_walls): q_a < 0 with the low face of a open, or q_a > 1 with the high face open: the record dies
+ *   5  q_a = c(q_a): a closed wall holds the particle on it
+ *   6  with a mask set (fx_set_obstacles): the cell i_a = min((int)(q_a * N_a), N_a - 1); if it is solid the position stays p, bits kept --
+ *      a particle does not enter a solid, and one that a moving solid has run over stays put until the solid has passed
+ *   7  age1 = age + dt;  lifetime > 0 and age1 >= lifetime: the record dies
+ *   8  stored: (the position of rule 5 or 6, a dying record's age = -1, a surviving one's = age1)
+ * fx_simulate runs the stage behind the projection, on the projected VELOCITY, when the time step is > 0 and a set exists; the step then
+ * never allocates, copies or synchronises for it (a captured fx_simulate stays capturable).  fx_move_particles is that stage alone: nothing
+ * (FX_OK) with no set or dt <= 0.  Timing: booked into fx_timing.project_ms.
+ * fx_set_particles replaces the set: records = float[count][4], host memory, or with FX_PARTICLES_DEVICE device memory of the context's device
+ * read by a copy enqueued on `stream`.  All allocation happens here; it returns once the records have been read.  count 0 (records may be
+ * NULL) frees the buffer and restores the default: every call then behaves exactly as without this function.
+ * fx_get_particles blocks like fx_download: *count gets the set's size, out (may be NULL with capacity 0) the first min(capacity, *count) records.
+ * fx_particles_device: the context's own buffer and count, for zero-copy drawing and respawning; valid until the next fx_set_particles or
+ * fx_destroy; (NULL, 0) with no set.  Either out-pointer may be NULL.
+ * fx_set_particle_params: NULL restores the defaults (midpoint, no drift, immortal).  fx_get_particle_params: the setting in force.
+ * fx_sample_velocity: points = float[count][4] (w is ignored: a particle buffer can be passed as it is), out = float[count][3] = U(point),
+ * read from FX_FIELD_VELOCITY (behind fx_simulate: the projected field).  Host pointers: copy in, launch, copy out, block.  With
+ * FX_PARTICLES_DEVICE both are device memory (points 16-byte aligned, out 4-byte): the launch is enqueued on `stream`, nothing else.
+ * count 0 returns FX_OK.
+ * Particles are caller data and configuration on the emitters' terms: per context, kept across fx_update_frame, not checkpointed (a caller
+ * saves them with fx_get_particles), not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx, a wrong struct_size, unknown flag bits, an unknown scheme, a non-finite
+ * drift, a non-finite or negative lifetime, count > FX_MAX_PARTICLES, count with a NULL pointer, a misaligned device pointer, and (every
+ * call but the three getters) a context that owns fewer planes than the grid -- slab ranks of every transport, on the confinement's footing;
+ * the getters succeed there and report the empty default, as fx_get_emitters does.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts.  FX_E_NOMEM:
+ * the buffer cannot be allocated.
+ * Out of scope: spawning on the device; sorting or binning on the device (a set sorted by cell on the host moves faster: DESIGN.md); drawing
+ * particles in the library's renders; two-way coupling; sampling colour or temperature at points. */
+#define FX_MAX_PARTICLES      (1u << 26)
+#define FX_PARTICLES_DEVICE   0x1u      /* the pointer(s) are device memory of the context's device */
+#define FX_PARTICLE_EULER     0u
+#define FX_PARTICLE_MIDPOINT  1u        /* default */
+typedef struct fx_particle_params {
+	uint32_t struct_size, flags;   /* sizeof(fx_particle_params) = 28; flags: 0 */
+	uint32_t scheme;               /* FX_PARTICLE_* */
+	float drift[3];                /* added to the sampled velocity, texture space per second (settling ash: negative y); default 0 */
+	float lifetime;                /* seconds; 0 = immortal (default); finite, >= 0 */
+} fx_particle_params;
+int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t count, uint32_t flags);
+int fx_get_particles(fx_ctx* ctx, float* out, uint32_t capacity, uint32_t* count);
+int fx_particles_device(fx_ctx* ctx, void** records, uint32_t* count);
+int fx_set_particle_params(fx_ctx* ctx, const fx_particle_params* params);
+int fx_get_particle_params(fx_ctx* ctx, fx_particle_params* out);
+int fx_move_particles(fx_ctx* ctx, void* stream);
+int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t count, float* out, uint32_t flags);
+
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
  * ch. 30): second order, unconditionally stable with its limiter, two more gathers per cell.  While it is set, the advection of fx_simulate
