@@ -97,6 +97,14 @@ class ParticleParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("scheme", C.c_uint32), ("drift", C.c_float * 3), ("lifetime", C.c_float)]
 
 
+class ParticleSort(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("enabled", C.c_uint32), ("every", C.c_uint32)]
+
+
+class ParticleSortInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("live", C.c_uint32), ("sorts", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("advect_ms", C.c_double), ("divergence_ms", C.c_double), ("jacobi_ms", C.c_double),
                 ("project_ms", C.c_double), ("light_ms", C.c_double), ("view_ms", C.c_double),
@@ -158,6 +166,11 @@ SYMBOLS = {
     "fx_get_particle_params": (C.c_int, [_vp, C.POINTER(ParticleParams)]),
     "fx_move_particles": (C.c_int, [_vp, _vp]),
     "fx_sample_velocity": (C.c_int, [_vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32]),
+    "fx_set_particle_sort": (C.c_int, [_vp, C.POINTER(ParticleSort)]),
+    "fx_get_particle_sort": (C.c_int, [_vp, C.POINTER(ParticleSort)]),
+    "fx_sort_particles": (C.c_int, [_vp, _vp]),
+    "fx_particle_sort_info": (C.c_int, [_vp, _vp, C.POINTER(ParticleSortInfo)]),
+    "fx_particle_order_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),
@@ -194,7 +207,7 @@ _lib = None
 # the launcher switches that exist in lab builds only (fx_knobs.cpp, -DFX_LAB)
 LAB_KNOBS = {"ADVECT_BLOCK", "ADVECT_FAST", "ADVECT_LDS_HALF", "ADVECT_TILE_ROWS", "ADVECT_ZCHUNK", "BLOCK_REMAP", "BLOCK_SHAPE", "DEBUG_NO_COPY",
              "FREEZE_DENSE_LEVELS", "FREEZE_DENSE_ONE", "FREEZE_FAST", "FREEZE_FUSE_DIV", "FREEZE_NT", "FREEZE_SHRINK", "FREEZE_T", "FREEZE_WGS",
-             "JACOBI2D_TILE", "JACOBI_BLOCK", "JACOBI_BLOCKG", "LIGHT_FILL_DIRTY", "LIGHT_RAY_NT", "LIGHT_RAY_WGS", "OBSTACLE_V4", "PROJECT_V4", "ROW_VW",
+             "JACOBI2D_TILE", "JACOBI_BLOCK", "JACOBI_BLOCKG", "LIGHT_FILL_DIRTY", "LIGHT_RAY_NT", "LIGHT_RAY_WGS", "OBSTACLE_V4", "PROJECT_V4", "PSORT_KEY_BITS", "ROW_VW",
              "STRIP3H_PAIRS", "STRIP3_COOP", "STRIP3_NO512", "STRIP3_OFF", "STRIP3_ZCHUNK", "STRIP4T", "STRIP4T_256", "STRIP4T_512", "STRIP4T_FROM", "STRIP4T_GRID", "STRIP4T_NARROW", "STRIP4T_NARROW_FROM", "STRIP4T_PIECES", "STRIP4X", "STRIP4X_MINP", "STRIP4X_NT", "STRIP4X_ORDER", "STRIP4X_WGS",
              "STRIP4_OCTET", "STRIP4_ZCHUNK", "STRIP4_ZFLOOR", "STRIP_GENERIC", "STRIP_R", "STRIP_REMAP", "STRIP_WGS", "STRIP_WIDE", "STRIP_ZCHUNK", "VIEW_ORDER", "VIEW_WGS", "VORT_ZCHUNK", "WIDE_OFFSETS", "XCD_REMAP"}
 

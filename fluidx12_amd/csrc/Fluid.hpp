@@ -217,6 +217,28 @@ public:
 		return m_status == FX_OK;
 	}
 
+	// not in the reference: the particle sort -- the buffer of ParticlesDevice sorted on the device by cell, stable, dead records last
+	// (fx_set_particle_sort: enabled allocates the scratch, every = n > 0 sorts in front of the move on every nth run of the particle stage;
+	// nullptr = off, the default), the stage alone (fx_sort_particles), what the last sort counted (fx_particle_sort_info: the live records
+	// occupy [0, live)) and the context's device arrays (fx_particle_order_device: order[i] = where the record now at i came from, and live)
+	bool SetParticleSort(const fx_particle_sort* sort) { m_status = fx_set_particle_sort(m_ctx, sort); return m_status == FX_OK; }
+	bool SetParticleSort(bool enabled, uint32_t every = 0)
+	{
+		const fx_particle_sort p = { (uint32_t)sizeof(fx_particle_sort), 0u, enabled ? 1u : 0u, every };
+		return SetParticleSort(&p);
+	}
+	bool GetParticleSort(fx_particle_sort& out) { m_status = fx_get_particle_sort(m_ctx, &out); return m_status == FX_OK; }
+	bool SortParticles(void* stream = nullptr) { m_status = fx_sort_particles(m_ctx, stream); return m_status == FX_OK; }
+	bool ParticleSortInfo(uint32_t& live, uint32_t& sorts, void* stream = nullptr)
+	{
+		struct fx_particle_sort_info r = { (uint32_t)sizeof(struct fx_particle_sort_info), 0u, 0u, 0u };
+		m_status = fx_particle_sort_info(m_ctx, stream, &r);
+		live = r.live; sorts = r.sorts;
+		return m_status == FX_OK;
+	}
+	bool ParticleOrderDevice(void*& order, void*& live) { m_status = fx_particle_order_device(m_ctx, &order, &live); return m_status == FX_OK; }
+	// (a host copy of order is the caller's own device-to-host copy: this header does not include the HIP runtime)
+
 	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
 	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }

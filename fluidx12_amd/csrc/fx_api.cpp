@@ -719,6 +719,21 @@ int fx_get_heat_sources(fx_ctx* ctx, fx_heat_source* out, uint32_t capacity, uin
 int fx_heat(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, heat_phase); }
 
 // ---- tracer particles and the point query (fx_particles.hip) ---------------------------------------------------
+// The sort's scratch block for `count` records of this grid (fx_particle_sort_plan.cpp lays it out), its live word zeroed; blocks.  FX_E_INVALID
+// for a grid the 32-bit key cannot number, FX_E_NOMEM; nothing of the context changes
+static int psort_alloc(fx_ctx* ctx, uint32_t count, fx::PsortPlan* plan, void** mem)
+{
+	const uint64_t cells = (uint64_t)ctx->g.X * (uint64_t)ctx->g.Y * (uint64_t)ctx->g.Zg;
+	if (fx::psort_plan(cells, count, FX_KNOB_INT("PSORT_KEY_BITS", 0), plan) != 0) return FX_E_INVALID;
+	*mem = nullptr;
+	if (hipMalloc(mem, plan->scratch_bytes) != hipSuccess) { (void)hipGetLastError(); *mem = nullptr; return FX_E_NOMEM; }
+	if (hipMemset(static_cast<char*>(*mem) + plan->off_live, 0, 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+		(void)hipGetLastError(); (void)hipFree(*mem); *mem = nullptr;
+		return FX_E_DEVICE;
+	}
+	return FX_OK;
+}
+
 // The set lives in a buffer of its own that only this call allocates and frees: the new one is filled beside the one in force, which stays in
 // force if anything fails.  Blocks until the caller's records have been read.
 int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t count, uint32_t flags)
@@ -728,17 +743,32 @@ int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t c
 	if (count > FX_MAX_PARTICLES || (count && !records)) return FX_E_INVALID;
 	DeviceGuard dg(ctx->device);
 	float* fresh = nullptr;
+	void* sort_mem = nullptr;                                               // while sorting is enabled: the scratch of the new count, on the same terms
+	fx::PsortPlan sort_plan = {};
+	if (ctx->psort_mem)
+		if (const int rc = psort_alloc(ctx, count, &sort_plan, &sort_mem)) return rc;
 	if (count) {
 		const size_t bytes = (size_t)count * 16;
-		if (hipMalloc((void**)&fresh, bytes) != hipSuccess) { (void)hipGetLastError(); return FX_E_NOMEM; }
+		if (hipMalloc((void**)&fresh, bytes) != hipSuccess) { (void)hipGetLastError(); if (sort_mem) (void)hipFree(sort_mem); return FX_E_NOMEM; }
 		hipStream_t s = pick_stream(ctx, stream);
 		hipError_t e = hipMemcpyAsync(fresh, records, bytes, (flags & FX_PARTICLES_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
 		if (e == hipSuccess) e = hipStreamSynchronize(s);
-		if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(fresh); ctx->last_error = std::string("fx_set_particles: ") + hipGetErrorString(e); return FX_E_DEVICE; }
+		if (e != hipSuccess) {
+			(void)hipGetLastError(); (void)hipFree(fresh);
+			if (sort_mem) (void)hipFree(sort_mem);
+			ctx->last_error = std::string("fx_set_particles: ") + hipGetErrorString(e);
+			return FX_E_DEVICE;
+		}
 	}
 	if (ctx->part) FX_HIP(hipFree(ctx->part));                              // (hipFree waits for the device: nothing moves the old set any more)
 	ctx->part = fresh;
 	ctx->part_count = count;
+	if (sort_mem) {
+		(void)hipFree(ctx->psort_mem);
+		ctx->psort_mem = sort_mem;
+		ctx->psort = sort_plan;
+	}
+	ctx->psort_runs = ctx->psort_sorts = 0;
 	return FX_OK;
 }
 
@@ -785,6 +815,68 @@ int fx_get_particle_params(fx_ctx* ctx, fx_particle_params* out)
 }
 
 int fx_move_particles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, particles_phase); }
+
+// ---- the particle sort (fx_particle_sort.hip) -------------------------------------------------------------------
+// Enabling allocates the scratch of the set in force (fx_set_particles resizes it from then on), disabling frees it; either way the stage's run
+// counter and the sort counter start again.  Blocks.
+int fx_set_particle_sort(fx_ctx* ctx, const fx_particle_sort* p)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	const fx_particle_sort def = { (uint32_t)sizeof(fx_particle_sort), 0u, 0u, 0u };
+	if (!p) p = &def;
+	if (p->struct_size != sizeof(fx_particle_sort) || p->flags != 0 || p->enabled > 1u || (p->every && !p->enabled)) return FX_E_INVALID;
+	DeviceGuard dg(ctx->device);
+	if (p->enabled && !ctx->psort_mem) {
+		void* mem = nullptr;
+		fx::PsortPlan plan = {};
+		if (const int rc = psort_alloc(ctx, ctx->part_count, &plan, &mem)) return rc;
+		ctx->psort_mem = mem;
+		ctx->psort = plan;
+	} else if (!p->enabled && ctx->psort_mem) {
+		FX_HIP(hipFree(ctx->psort_mem));                                    // (waits for the device: no sort is in flight any more)
+		ctx->psort_mem = nullptr;
+		ctx->psort = fx::PsortPlan{};
+	}
+	ctx->psort_cfg = *p;
+	ctx->psort_runs = ctx->psort_sorts = 0;
+	return FX_OK;
+}
+
+int fx_get_particle_sort(fx_ctx* ctx, fx_particle_sort* out)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!out) return FX_E_INVALID;
+	*out = ctx->psort_cfg;
+	return FX_OK;
+}
+
+int fx_sort_particles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, sort_particles_phase); }
+
+int fx_particle_sort_info(fx_ctx* ctx, void* stream, struct fx_particle_sort_info* out)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!out) return FX_E_INVALID;
+	struct fx_particle_sort_info r = { (uint32_t)sizeof(struct fx_particle_sort_info), 0u, ctx->psort_sorts, 0u };
+	if (ctx->psort_mem) {
+		DeviceGuard dg(ctx->device);
+		hipStream_t s = pick_stream(ctx, stream);
+		FX_HIP(hipMemcpyAsync(&r.live, static_cast<char*>(ctx->psort_mem) + ctx->psort.off_live, 4, hipMemcpyDeviceToHost, s));
+		FX_HIP(hipStreamSynchronize(s));
+	}
+	*out = r;
+	return FX_OK;
+}
+
+int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (!order_u32 || !live_u32) return FX_E_INVALID;
+	if (!ctx->psort_mem) return FX_E_STATE;
+	char* m = static_cast<char*>(ctx->psort_mem);
+	*order_u32 = ctx->part_count ? m + ctx->psort.off_order : nullptr;
+	*live_u32 = m + ctx->psort.off_live;
+	return FX_OK;
+}
 
 int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t count, float* out, uint32_t flags)
 {

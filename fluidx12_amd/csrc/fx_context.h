@@ -106,6 +106,13 @@ struct fx_ctx {
 	float* part = nullptr;          // device; null = no set: every call is the one it is without particles
 	uint32_t part_count = 0;
 	fx_particle_params part_prm = { (uint32_t)sizeof(fx_particle_params), 0u, FX_PARTICLE_MIDPOINT, { 0.0f, 0.0f, 0.0f }, 0.0f };
+	// the particle sort (fx_set_particle_sort; fx_particle_sort.hip): while enabled, one scratch block laid out by psort (order, live, keys,
+	// indices, a record array, histograms), allocated and freed by fx_set_particle_sort and fx_set_particles alone
+	fx_particle_sort psort_cfg = { (uint32_t)sizeof(fx_particle_sort), 0u, 0u, 0u };
+	void* psort_mem = nullptr;      // device; null = sorting is off
+	fx::PsortPlan psort = {};       // of the grid and part_count, while psort_mem is set
+	uint32_t psort_runs = 0;        // runs of the particle stage since the last fx_set_particles / fx_set_particle_sort (what `every` counts)
+	uint32_t psort_sorts = 0;       // sorts enqueued since then
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

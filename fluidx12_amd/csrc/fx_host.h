@@ -109,6 +109,7 @@ int jacobi_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s, uint32_t it
 int pressure_solve_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s);   // the solver stage of the step: jacobi_all(jacobi_iters), or the multigrid V-cycles (fx_set_pressure_solver)
 int project_phase(fx_ctx* ctx, hipStream_t s);
 int particles_phase(fx_ctx* ctx, hipStream_t s);     // the tracer particles one step through velocity[0], behind the projection; nothing with no set or dt <= 0
+int sort_particles_phase(fx_ctx* ctx, hipStream_t s);   // the particle sort alone (fx_sort_particles); nothing with no set; counts into psort_sorts
 int simulate_impl(fx_ctx* ctx, hipStream_t s);
 
 }  // namespace fxh

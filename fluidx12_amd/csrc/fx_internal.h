@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include "../../include/fluidx_hip.h"
 #include "fx_knobs.h"
+#include "fx_particle_sort_plan.h"
 
 namespace fx {
 
@@ -209,6 +210,10 @@ hipError_t launch_move_particles(const Geom& g, int half_store, const fx_particl
 	float dt, float* records, uint32_t count, hipStream_t s);
 // points: count x float4 (w ignored), out: count x 3 floats, both device memory; out = the stored velocity vel0 sampled as the particles sample it
 hipError_t launch_sample_velocity(const Geom& g, int half_store, const void* vel0, const float* points, float* out, uint32_t count, hipStream_t s);
+// ---- the particle sort (fx_particle_sort.hip; fx_set_particle_sort, fx_sort_particles): records sorted in place by cell, dead ones last, stable;
+// p: psort_plan of this grid and count (fx_particle_sort_plan.cpp), scratch: p.scratch_bytes of device memory laid out as p says -- order and
+// live are read there.  Enqueues only; reads and writes the records and the scratch, nothing else.  count 0 is the caller's to skip
+hipError_t launch_particle_sort(const Geom& g, const PsortPlan& p, float* records, void* scratch, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

@@ -28,6 +28,7 @@
 // field is under 4 GiB, 64-bit ones above (WIDE).
 #include "fx_internal.h"
 #include "fx_store.h"
+#include "fx_particle_cell.h"
 
 namespace fx {
 
@@ -38,7 +39,6 @@ namespace {
 const int PT_WG = 256;
 
 __device__ __forceinline__ float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
 // two adjacent cells of a plane in one load, at the alignment of one cell
 struct __attribute__((packed, aligned(4))) PairF { float a, b; };
@@ -158,8 +158,8 @@ __global__ __launch_bounds__(256) void k_move_particles(const Geom geo, const Pa
 	if (IS3D) qz = clamp01(qz) + 0.0f;
 
 	if (code) {                                                         // a record does not enter a solid
-		const int cx = min((int)(qx * (float)g.X), g.X - 1), cy = min((int)(qy * (float)g.Y), g.Y - 1);
-		const int cz = IS3D ? min((int)(qz * (float)g.Z), g.Z - 1) : 0;
+		const int cx = cell_axis(qx, g.X), cy = cell_axis(qy, g.Y);
+		const int cz = IS3D ? cell_axis(qz, g.Z) : 0;
 		const size_t cell = ((size_t)cz * (size_t)g.Y + (size_t)cy) * (size_t)g.X + (size_t)cx;
 		if (code[cell] & 64u) { qx = r.x; qy = r.y; qz = r.z; }
 	}

@@ -816,7 +816,29 @@ int particles_phase(fx_ctx* ctx, hipStream_t s)
 	if (!ctx->part || !(ctx->time_step > 0.0f)) return FX_OK;
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_PROJECT);
+	// the sort, when this run is due one (fx_set_particle_sort's `every`: the 1st, (n+1)th ... run of this stage), in front of the move: the step
+	// that pays for it gets the coherent gathers.  Decided here, at enqueue time: a captured step replays what was captured
+	if (ctx->psort_mem && ctx->psort_cfg.every) {
+		const bool due = ctx->psort_runs % ctx->psort_cfg.every == 0;
+		++ctx->psort_runs;
+		if (due) {
+			FX_HIP(launch_particle_sort(ctx->g, ctx->psort, ctx->part, ctx->psort_mem, s));
+			++ctx->psort_sorts;
+		}
+	}
 	FX_HIP(launch_move_particles(ctx->g, ctx->half, ctx->part_prm, ctx->vel[0], ctx->obst_code, ctx->open_faces, ctx->time_step, ctx->part, ctx->part_count, s));
+	return FX_OK;
+}
+
+// The particle sort alone (fx_particle_sort.hip): the records by cell, the dead last, order and live left in the scratch block.  Enqueues only.
+int sort_particles_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->psort_mem) return FX_E_STATE;
+	if (!ctx->part) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_PROJECT);
+	FX_HIP(launch_particle_sort(ctx->g, ctx->psort, ctx->part, ctx->psort_mem, s));
+	++ctx->psort_sorts;
 	return FX_OK;
 }
 

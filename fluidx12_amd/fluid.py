@@ -612,6 +612,61 @@ class Fluid:
         self._need()
         capi.check(self._lib.fx_move_particles(self._ctx, stream), "MoveParticles")
 
+    def SetParticleSort(self, enabled, every=0, flags=0):
+        """the particle sort (fx_set_particle_sort): `enabled` allocates the sort's scratch for the set in force and every later one (False
+        frees it, the default); `every` = n > 0 lets the particle stage sort in front of the move on its 1st, (n+1)th ... run, 0 leaves
+        sorting to SortParticles.  The sort is stable, by cell, dead records last.  SetParticleSort(None) restores the default."""
+        self._need()
+        if enabled is None:
+            capi.check(self._lib.fx_set_particle_sort(self._ctx, None), "SetParticleSort")
+            return
+        p = capi.ParticleSort()
+        p.struct_size, p.flags, p.enabled, p.every = C.sizeof(capi.ParticleSort), int(flags), int(enabled), int(every)
+        capi.check(self._lib.fx_set_particle_sort(self._ctx, C.byref(p)), "SetParticleSort")
+
+    def GetParticleSort(self):
+        """the setting in force (fx_get_particle_sort) as a dict with SetParticleSort's keys"""
+        self._need()
+        p = capi.ParticleSort()
+        capi.check(self._lib.fx_get_particle_sort(self._ctx, C.byref(p)), "GetParticleSort")
+        return {"enabled": bool(p.enabled), "every": p.every, "flags": p.flags}
+
+    def SortParticles(self, stream=None):
+        """the sort alone (fx_sort_particles): the buffer of ParticlesDevice() by cell, the dead last; enqueues only"""
+        self._need()
+        capi.check(self._lib.fx_sort_particles(self._ctx, stream), "SortParticles")
+
+    def ParticleSortInfo(self, stream=None):
+        """(live, sorts) (fx_particle_sort_info; waits for the stream): the live records the last sort counted -- they occupy [0, live) --
+        and the sorts enqueued since the last SetParticles / SetParticleSort"""
+        self._need()
+        r = capi.ParticleSortInfo()
+        r.struct_size = C.sizeof(capi.ParticleSortInfo)
+        capi.check(self._lib.fx_particle_sort_info(self._ctx, stream, C.byref(r)), "ParticleSortInfo")
+        return int(r.live), int(r.sorts)
+
+    def ParticleOrderDevice(self):
+        """(device address of order, device address of live) (fx_particle_order_device): order[i] = the index the record now at i had before
+        the last sort, uint32 per record (0 with no set); live = one uint32.  Valid until the next SetParticles / SetParticleSort"""
+        self._need()
+        o, l = C.c_void_p(None), C.c_void_p(None)
+        capi.check(self._lib.fx_particle_order_device(self._ctx, C.byref(o), C.byref(l)), "ParticleOrderDevice")
+        return int(o.value or 0), int(l.value or 0)
+
+    def ParticleOrder(self):
+        """a host copy of order (numpy uint32, one per record), for tests and host callers; blocks like download"""
+        self._need()
+        o, _ = self.ParticleOrderDevice()
+        _, n = self.ParticlesDevice()
+        out = np.empty(n, np.uint32)
+        if n and o:
+            lib = self._lib                                  # the HIP runtime the library itself is linked against
+            lib.hipDeviceSynchronize.restype, lib.hipDeviceSynchronize.argtypes = C.c_int, []
+            lib.hipMemcpy.restype, lib.hipMemcpy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            if lib.hipDeviceSynchronize() != 0 or lib.hipMemcpy(out.ctypes.data, o, out.nbytes, 2) != 0:      # 2: hipMemcpyDeviceToHost
+                raise RuntimeError("ParticleOrder: the copy from the device failed")
+        return out
+
     def SampleVelocity(self, points, stream=None, out=None):
         """the velocity at points of texture space (fx_sample_velocity): `points` (n, 3) or (n, 4) (a fourth column is ignored) as anything numpy
         takes -> float32 (n, 3), blocking; or a float32 torch tensor (n, 4) on the context's device with `out` a float32 tensor (n, 3) there:

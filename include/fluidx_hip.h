@@ -611,7 +611,7 @@ int fx_heat(fx_ctx* ctx, void* stream);
  * call but the three getters) a context that owns fewer planes than the grid -- slab ranks of every transport, on the confinement's footing;
  * the getters succeed there and report the empty default, as fx_get_emitters does.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts.  FX_E_NOMEM:
  * the buffer cannot be allocated.
- * Out of scope: spawning on the device; sorting or binning on the device (a set sorted by cell on the host moves faster: DESIGN.md); drawing
+ * Out of scope: spawning on the device; drawing
  * particles in the library's renders; two-way coupling; sampling colour or temperature at points. */
 #define FX_MAX_PARTICLES      (1u << 26)
 #define FX_PARTICLES_DEVICE   0x1u      /* the pointer(s) are device memory of the context's device */
@@ -630,6 +630,56 @@ int fx_set_particle_params(fx_ctx* ctx, const fx_particle_params* params);
 int fx_get_particle_params(fx_ctx* ctx, fx_particle_params* out);
 int fx_move_particles(fx_ctx* ctx, void* stream);
 int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t count, float* out, uint32_t flags);
+
+/* The particle sort (no reference counterpart).  The move above is a scattered gather: how fast it runs depends on the order of the buffer,
+ * and a set in cell order moves many times faster than a shuffled one.  This stage sorts the buffer on the device: a
+ * stable sort by cell with the dead records last, which also leaves the number of live records in device memory, so that respawning is an
+ * append.  One stable radix sort of (key, index) pairs and one gather of the records (fx_particle_sort.hip); no atomic decides a position, the
+ * result is the same bit for bit on every run.
+ * The rule (tests/particle_sort_ref.py restates it in numpy), for a record r = (x, y, z, age) on a grid N = (X, Y, Z):
+ *   live   iff age >= 0 -- the move's own test: a negative or NaN age is dead, -0.0 is live
+ *   cell   per axis, fp32, each operation rounded as written: c_a = min((int)(c(p_a) * (float)N_a), N_a - 1), c(v) = fminf(fmaxf(v, 0), 1):
+ *          the formula of the move's solid lookup (rule 6).  A NaN position lands in cell 0, 1.0 in N_a - 1.  A 2-D grid does not look at
+ *          z: c_z = 0
+ *   key    (c_z * Y + c_y) * X + c_x for a live record, X * Y * Z for a dead one; a uint32
+ *   sort   the buffer becomes rec[order], order = the stable ascending permutation of the keys (numpy: argsort(key, kind="stable")).  Every
+ *          record moves with all 128 bits intact: dead records keep their bits, NaN payloads included, and their relative order; live
+ *          records of one cell keep theirs
+ *   live   = the number of live records: behind a sort they occupy [0, live), the dead [live, count)
+ * The buffer stays where it is: fx_particles_device returns the same pointer before and behind a sort, and it holds the sorted set.
+ * fx_set_particle_sort: NULL = the default (off).  enabled = 1 allocates the sort's scratch for the set in force, and fx_set_particles
+ * resizes it with every later set (FX_E_NOMEM there leaves the previous set and scratch in force); enabled = 0 frees it.  All allocation and
+ * waiting happens in these two calls: fx_sort_particles and the step only enqueue (a captured fx_simulate stays capturable).  every = n > 0:
+ * the particle stage (fx_simulate, fx_move_particles) sorts in front of the move on its 1st, (n+1)th, (2n+1)th ... run, counted from the last
+ * fx_set_particles / fx_set_particle_sort, so the step that pays for the sort also gets the coherent gathers; every = 0: only
+ * fx_sort_particles sorts.  Whether a run sorts is decided on the host when it is enqueued: a captured step replays what was captured,
+ * with or without the sort, however often it is replayed.  Timing: booked into fx_timing.project_ms, like the move.
+ * fx_sort_particles: the stage alone.  FX_OK and nothing done while no set exists.
+ * fx_particle_sort_info waits for `stream`: live = what the last sort counted (0 before the first), sorts = sorts enqueued since the last
+ * fx_set_particles / fx_set_particle_sort.  With sorting off both are 0.
+ * fx_particle_order_device: the context's own device arrays.  order_u32[i] = the index the record now at i had before the last sort -- what
+ * a caller needs to carry per-particle arrays of its own (colour, size, id) along, with a gather kernel on the same stream; valid once
+ * sorts > 0, until the next sort or fx_set_particles (NULL while no set exists).  live_u32 = one uint32, rewritten by every sort.  Respawning:
+ * a caller's kernel on the steps' stream reads *live_u32 and writes its new records to [live, count).
+ * The sort reads and writes the particle buffer and its own scratch, nothing else: no field, no obstacle code.  Configuration on the
+ * particles' terms: per context, kept across fx_update_frame, not checkpointed, not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx, a wrong struct_size, unknown flag bits, enabled > 1, every > 0 with
+ * enabled = 0, a NULL out-pointer, a grid of 2^32 - 1 cells or more, and (all but fx_get_particle_sort and fx_particle_sort_info, which
+ * report the default there) slab ranks.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts; fx_sort_particles and fx_particle_order_device while
+ * sorting is not enabled.  FX_E_NOMEM: the scratch cannot be allocated.
+ * (struct fx_particle_sort_info has no typedef: C keeps a typedef and the function of that name in one name space.)
+ * Out of scope: spawning on the device; other orders (Morton, tiles); sorting by anything but cell; slab contexts. */
+typedef struct fx_particle_sort {
+	uint32_t struct_size, flags;   /* sizeof(fx_particle_sort) = 16; flags: 0 */
+	uint32_t enabled;              /* 0 (default): no scratch, no sort anywhere; 1: scratch allocated for the current and every later set */
+	uint32_t every;                /* with enabled: 0 = only fx_sort_particles sorts; n > 0 = the particle stage sorts on every nth run */
+} fx_particle_sort;
+struct fx_particle_sort_info { uint32_t struct_size, live, sorts, reserved; };   /* 16 bytes */
+int fx_set_particle_sort(fx_ctx* ctx, const fx_particle_sort* sort);
+int fx_get_particle_sort(fx_ctx* ctx, fx_particle_sort* out);
+int fx_sort_particles(fx_ctx* ctx, void* stream);
+int fx_particle_sort_info(fx_ctx* ctx, void* stream, struct fx_particle_sort_info* out);
+int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32);
 
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
