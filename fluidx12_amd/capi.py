@@ -105,6 +105,10 @@ class ParticleSortInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("live", C.c_uint32), ("sorts", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ParticleTrail(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("rate", C.c_float), ("tint", C.c_float * 4), ("heat", C.c_float)]
+
+
 class Timing(C.Structure):
     _fields_ = [("advect_ms", C.c_double), ("divergence_ms", C.c_double), ("jacobi_ms", C.c_double),
                 ("project_ms", C.c_double), ("light_ms", C.c_double), ("view_ms", C.c_double),
@@ -171,6 +175,10 @@ SYMBOLS = {
     "fx_sort_particles": (C.c_int, [_vp, _vp]),
     "fx_particle_sort_info": (C.c_int, [_vp, _vp, C.POINTER(ParticleSortInfo)]),
     "fx_particle_order_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "fx_set_particle_trail": (C.c_int, [_vp, C.POINTER(ParticleTrail)]),
+    "fx_get_particle_trail": (C.c_int, [_vp, C.POINTER(ParticleTrail)]),
+    "fx_deposit_particles": (C.c_int, [_vp, _vp]),
+    "fx_particle_density": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.c_size_t]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),
@@ -209,7 +217,7 @@ LAB_KNOBS = {"ADVECT_BLOCK", "ADVECT_FAST", "ADVECT_LDS_HALF", "ADVECT_TILE_ROWS
              "FREEZE_DENSE_LEVELS", "FREEZE_DENSE_ONE", "FREEZE_FAST", "FREEZE_FUSE_DIV", "FREEZE_NT", "FREEZE_SHRINK", "FREEZE_T", "FREEZE_WGS",
              "JACOBI2D_TILE", "JACOBI_BLOCK", "JACOBI_BLOCKG", "LIGHT_FILL_DIRTY", "LIGHT_RAY_NT", "LIGHT_RAY_WGS", "OBSTACLE_V4", "PROJECT_V4", "PSORT_KEY_BITS", "ROW_VW",
              "STRIP3H_PAIRS", "STRIP3_COOP", "STRIP3_NO512", "STRIP3_OFF", "STRIP3_ZCHUNK", "STRIP4T", "STRIP4T_256", "STRIP4T_512", "STRIP4T_FROM", "STRIP4T_GRID", "STRIP4T_NARROW", "STRIP4T_NARROW_FROM", "STRIP4T_PIECES", "STRIP4X", "STRIP4X_MINP", "STRIP4X_NT", "STRIP4X_ORDER", "STRIP4X_WGS",
-             "STRIP4_OCTET", "STRIP4_ZCHUNK", "STRIP4_ZFLOOR", "STRIP_GENERIC", "STRIP_R", "STRIP_REMAP", "STRIP_WGS", "STRIP_WIDE", "STRIP_ZCHUNK", "VIEW_ORDER", "VIEW_WGS", "VORT_ZCHUNK", "WIDE_OFFSETS", "XCD_REMAP"}
+             "STRIP4_OCTET", "STRIP4_ZCHUNK", "STRIP4_ZFLOOR", "STRIP_GENERIC", "STRIP_R", "STRIP_REMAP", "STRIP_WGS", "STRIP_WIDE", "STRIP_ZCHUNK", "TRAIL_MERGE", "VIEW_ORDER", "VIEW_WGS", "VORT_ZCHUNK", "WIDE_OFFSETS", "XCD_REMAP"}
 
 
 def lib_path():

@@ -239,6 +239,23 @@ public:
 	bool ParticleOrderDevice(void*& order, void*& live) { m_status = fx_particle_order_device(m_ctx, &order, &live); return m_status == FX_OK; }
 	// (a host copy of order is the caller's own device-to-host copy: this header does not include the HIP runtime)
 
+	// not in the reference: the particle trail -- the particles as a source of smoke and heat (fx_set_particle_trail: every live particle
+	// spreads `rate` per second over the eight cells around it, COLOR grows by tint and TEMPERATURE by heat per unit; nullptr = off, the
+	// default), the stage alone (fx_deposit_particles) and the scatter alone copied to the host (fx_particle_density: uint64[Z][Y][X])
+	bool SetParticleTrail(const fx_particle_trail* trail) { m_status = fx_set_particle_trail(m_ctx, trail); return m_status == FX_OK; }
+	bool SetParticleTrail(float rate, const float tint[4], float heat = 0.0f)
+	{
+		const fx_particle_trail t = { (uint32_t)sizeof(fx_particle_trail), 0u, rate, { tint[0], tint[1], tint[2], tint[3] }, heat };
+		return SetParticleTrail(&t);
+	}
+	bool GetParticleTrail(fx_particle_trail& out) { m_status = fx_get_particle_trail(m_ctx, &out); return m_status == FX_OK; }
+	bool DepositParticles(void* stream = nullptr) { m_status = fx_deposit_particles(m_ctx, stream); return m_status == FX_OK; }
+	bool ParticleDensity(uint64_t* out, size_t bytes, void* stream = nullptr)
+	{
+		m_status = fx_particle_density(m_ctx, stream, out, bytes);
+		return m_status == FX_OK;
+	}
+
 	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
 	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }

@@ -878,6 +878,66 @@ int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32)
 	return FX_OK;
 }
 
+// ---- the particle trail (fx_particle_trail.hip) -----------------------------------------------------------------
+// The accumulator is allocated, zeroed, by the first call that sets a trail and freed by NULL; a later call replaces the rates and keeps it (it is
+// all zero between calls).  Blocks.
+int fx_set_particle_trail(fx_ctx* ctx, const fx_particle_trail* t)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	DeviceGuard dg(ctx->device);
+	if (!t) {
+		if (ctx->trail_acc) FX_HIP(hipFree(ctx->trail_acc));                // (hipFree waits for the device: no deposit is in flight any more)
+		ctx->trail_acc = nullptr;
+		const fx_particle_trail off = { (uint32_t)sizeof(fx_particle_trail), 0u, 0.0f, { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f };
+		ctx->trail = off;
+		return FX_OK;
+	}
+	if (t->struct_size != sizeof(fx_particle_trail) || t->flags != 0) return FX_E_INVALID;
+	if (!std::isfinite(t->rate) || t->rate < 0.0f || !std::isfinite(t->heat)) return FX_E_INVALID;
+	for (int a = 0; a < 4; ++a) if (!std::isfinite(t->tint[a])) return FX_E_INVALID;
+	if (!ctx->trail_acc) {
+		const size_t bytes = ctx->g.cells_owned() * sizeof(unsigned long long);
+		unsigned long long* acc = nullptr;
+		if (hipMalloc((void**)&acc, bytes) != hipSuccess) { (void)hipGetLastError(); return FX_E_NOMEM; }
+		hipError_t e = hipMemsetAsync(acc, 0, bytes, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(acc); return FX_E_DEVICE; }
+		ctx->trail_acc = acc;
+	}
+	ctx->trail = *t;
+	return FX_OK;
+}
+
+int fx_get_particle_trail(fx_ctx* ctx, fx_particle_trail* out)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!out) return FX_E_INVALID;
+	*out = ctx->trail;
+	return FX_OK;
+}
+
+int fx_deposit_particles(fx_ctx* ctx, void* stream)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (!ctx->trail_acc) return FX_E_STATE;
+	return trail_phase(ctx, pick_stream(ctx, stream));
+}
+
+// The scatter alone, the accumulator copied out and cleared again; blocks.  (The stage buffer is not used: the copy goes straight to the caller.)
+int fx_particle_density(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (!out || bytes != ctx->g.cells_owned() * sizeof(uint64_t)) return FX_E_INVALID;
+	if (!ctx->trail_acc) return FX_E_STATE;
+	hipStream_t s = pick_stream(ctx, stream);
+	if (const int rc = trail_splat_phase(ctx, s)) return rc;
+	DeviceGuard dg(ctx->device);
+	FX_HIP(hipMemcpyAsync(out, ctx->trail_acc, bytes, hipMemcpyDeviceToHost, s));
+	FX_HIP(hipMemsetAsync(ctx->trail_acc, 0, bytes, s));
+	FX_HIP(hipStreamSynchronize(s));
+	return FX_OK;
+}
+
 int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t count, float* out, uint32_t flags)
 {
 	if (const int rc = sim_guard(ctx)) return rc;

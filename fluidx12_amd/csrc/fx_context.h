@@ -113,6 +113,10 @@ struct fx_ctx {
 	fx::PsortPlan psort = {};       // of the grid and part_count, while psort_mem is set
 	uint32_t psort_runs = 0;        // runs of the particle stage since the last fx_set_particles / fx_set_particle_sort (what `every` counts)
 	uint32_t psort_sorts = 0;       // sorts enqueued since then
+	// the particle trail (fx_set_particle_trail; fx_particle_trail.hip): while set, one uint64 per cell, all zero between calls; allocated and
+	// freed by fx_set_particle_trail alone
+	fx_particle_trail trail = { (uint32_t)sizeof(fx_particle_trail), 0u, 0.0f, { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f };
+	unsigned long long* trail_acc = nullptr;   // device; null = no trail: every call is the one it is without the feature
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

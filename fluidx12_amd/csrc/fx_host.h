@@ -110,6 +110,8 @@ int pressure_solve_all(fx_ctx* lead, std::vector<fx_ctx*>& M, hipStream_t s);   
 int project_phase(fx_ctx* ctx, hipStream_t s);
 int particles_phase(fx_ctx* ctx, hipStream_t s);     // the tracer particles one step through velocity[0], behind the projection; nothing with no set or dt <= 0
 int sort_particles_phase(fx_ctx* ctx, hipStream_t s);   // the particle sort alone (fx_sort_particles); nothing with no set; counts into psort_sorts
+int trail_phase(fx_ctx* ctx, hipStream_t s);         // the particle trail (fx_deposit_particles): scatter and apply; nothing with no trail, no set or dt <= 0
+int trail_splat_phase(fx_ctx* ctx, hipStream_t s);   // the scatter alone (fx_particle_density); FX_E_STATE with no trail, nothing with no set
 int simulate_impl(fx_ctx* ctx, hipStream_t s);
 
 }  // namespace fxh

@@ -214,6 +214,13 @@ hipError_t launch_sample_velocity(const Geom& g, int half_store, const void* vel
 // p: psort_plan of this grid and count (fx_particle_sort_plan.cpp), scratch: p.scratch_bytes of device memory laid out as p says -- order and
 // live are read there.  Enqueues only; reads and writes the records and the scratch, nothing else.  count 0 is the caller's to skip
 hipError_t launch_particle_sort(const Geom& g, const PsortPlan& p, float* records, void* scratch, hipStream_t s);
+// ---- the particle trail (fx_particle_trail.hip; fx_set_particle_trail, fx_deposit_particles, fx_particle_density).  acc: one uint64 per cell,
+// all zero between calls.  splat: every live record adds its 2^24 of integer weights to the cells around it (count 0 is the caller's to skip);
+// apply: the cells with acc != 0 add to col (and to temp unless it is null), store their alpha to `alpha` unless it is null, and clear their
+// word; code: the obstacle code or null.  Both enqueue only
+hipError_t launch_trail_splat(const Geom& g, const float* records, uint32_t count, unsigned long long* acc, hipStream_t s);
+hipError_t launch_trail_apply(const Geom& g, int half_store, const fx_particle_trail& t, float dt, unsigned long long* acc, void* col, float* temp,
+	float* alpha, const uint8_t* code, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

@@ -1,5 +1,5 @@
 // fx_particle_cell.h -- the two primitives the particle kernels share (fx_particles.hip: the move and the point query; fx_particle_sort.hip:
-// the sort key): the clamp that stands in front of every index a record's position forms, and the cell of a clamped coordinate.  Device code only.
+// the sort key; fx_particle_trail.hip: the scatter's taps): the clamp that stands in front of every index a record's position forms, and the cell of a clamped coordinate.  Device code only.
 #pragma once
 
 namespace fx {

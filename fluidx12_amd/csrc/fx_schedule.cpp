@@ -356,6 +356,36 @@ int heat_phase(fx_ctx* ctx, hipStream_t s)
 	return FX_OK;
 }
 
+// The particle trail (fx_particle_trail.hip): behind buoyancy, in front of the enforce pass.  Colour and temperature are final for the step
+// here -- the deposit does not enter this step's buoyancy force: heat left now lifts from the next step on --, and the enforce pass behind it
+// has nothing to clear that the pass's own solid test did not keep out.  The positions are the ones the buffer holds now: moved at the end of
+// the previous step, or set by the caller.  Two launches, the scatter over the records and the apply over the grid, booked with the advection
+// like the neighbours; the temperature is the current buffer (heat_phase has swapped already), in place.  Nothing is allocated, copied or
+// waited for (fx_set_particle_trail did that); it keeps the render's alpha side volume true on the emitters' condition.
+int trail_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->trail_acc || !ctx->part || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	FX_HIP(launch_trail_splat(ctx->g, ctx->part, ctx->part_count, ctx->trail_acc, s));
+	float* temp = ctx->buoy_on && ctx->temp[0] && ctx->trail.heat != 0.0f ? ctx->temp[ctx->temp_cur] : nullptr;
+	FX_HIP(launch_trail_apply(ctx->g, ctx->half, ctx->trail, ctx->time_step, ctx->trail_acc, ctx->col[ctx->frame_parity], temp, alpha_mirror(ctx),
+		ctx->obst_code, s));
+	return FX_OK;
+}
+
+// The scatter alone, for fx_particle_density: the accumulator is left holding the set's weights (the caller copies and clears it).  Booked like
+// the stage, so that tools/particle_trail_bench.py can time the scatter apart from the apply.
+int trail_splat_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->trail_acc) return FX_E_STATE;
+	if (!ctx->part) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_ADVECT);
+	FX_HIP(launch_trail_splat(ctx->g, ctx->part, ctx->part_count, ctx->trail_acc, s));
+	return FX_OK;
+}
+
 // Solid obstacles (fx_obstacle.hip): behind the advection and the emitters, in front of the confinement, the solid cells of the advected velocity
 // and colour become +0, in place -- one launch over the solids' bounding box, booked with the advection like the two passes around it.  When this
 // step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well (the emitters' condition).
@@ -845,8 +875,9 @@ int sort_particles_phase(fx_ctx* ctx, hipStream_t s)
 // The optional stages between the advection and the divergence, each a no-op unless its feature is set (whole-grid contexts only: the setters
 // refuse slab ranks).  The order is the contract, every phase's own comment gives its half of it: the inflow pass scales what the advection
 // sampled, before the emitters add to it; buoyancy reads the alpha the emitters added; the enforce pass clears the solid cells of everything
-// added so far; the confinement comes last because it writes into velocity[0], the field the inflow pass and buoyancy trace with.
-static int (*const kOptionalStages[])(fx_ctx*, hipStream_t) = { open_inflow_phase, emit_phase, heat_phase, enforce_phase, confine_phase };
+// added so far; the confinement comes last because it writes into velocity[0], the field the inflow pass and buoyancy trace with.  The
+// particle trail stands behind buoyancy, whose force it does not enter, and in front of the enforce pass.
+static int (*const kOptionalStages[])(fx_ctx*, hipStream_t) = { open_inflow_phase, emit_phase, heat_phase, trail_phase, enforce_phase, confine_phase };
 
 int simulate_impl(fx_ctx* ctx, hipStream_t s)
 {

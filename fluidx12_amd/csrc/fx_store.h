@@ -1,5 +1,5 @@
 // fx_store.h -- how the optional stages of the step (fx_vorticity.hip, fx_emit.hip, fx_obstacle.hip, fx_heat.hip, fx_open.hip) the MacCormack
-// advection (fx_maccormack.hip), the multigrid pressure solver (fx_multigrid.hip) and the tracer particles (fx_particles.hip) read and write a
+// advection (fx_maccormack.hip), the multigrid pressure solver (fx_multigrid.hip), the tracer particles (fx_particles.hip) and their trail (fx_particle_trail.hip) read and write a
 // stored field: fp32, or binary16 widened on load and rounded once (RNE) on store.  Device code only: included by those files, never by
 // fx_internal.h (host-only programs include that one).  The kernels of fx_sim.hip keep their own Store<HALF>, the original of the device below.
 #pragma once

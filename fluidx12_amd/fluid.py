@@ -667,6 +667,40 @@ class Fluid:
                 raise RuntimeError("ParticleOrder: the copy from the device failed")
         return out
 
+    def SetParticleTrail(self, rate, tint=(0.0, 0.0, 0.0, 0.0), heat=0.0, flags=0):
+        """the particle trail (fx_set_particle_trail): every live particle spreads `rate` units of amount per second tri-linearly over the eight
+        cells around it; COLOR grows by `tint` (r, g, b, a) per unit amount and, while buoyancy is on, TEMPERATURE by `heat` per unit amount.
+        Simulate then deposits between the buoyancy pass and the obstacles' enforce pass.  Allocates one uint64 per cell.  SetParticleTrail(None)
+        switches it off (the default) and frees that.  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole-grid contexts only."""
+        self._need()
+        if rate is None:
+            capi.check(self._lib.fx_set_particle_trail(self._ctx, None), "SetParticleTrail")
+            return
+        t = capi.ParticleTrail()
+        t.struct_size, t.flags, t.rate, t.heat = C.sizeof(capi.ParticleTrail), int(flags), float(rate), float(heat)
+        t.tint = (C.c_float * 4)(*[float(v) for v in tint])
+        capi.check(self._lib.fx_set_particle_trail(self._ctx, C.byref(t)), "SetParticleTrail")
+
+    def GetParticleTrail(self):
+        """the setting in force (fx_get_particle_trail) as a dict with SetParticleTrail's keys; off: rate 0, tint 0, heat 0"""
+        self._need()
+        t = capi.ParticleTrail()
+        capi.check(self._lib.fx_get_particle_trail(self._ctx, C.byref(t)), "GetParticleTrail")
+        return {"rate": t.rate, "tint": tuple(t.tint), "heat": t.heat, "flags": t.flags}
+
+    def DepositParticles(self, stream=None):
+        """the trail stage alone (fx_deposit_particles): the particles where they are now add to COLOR and TEMPERATURE; enqueues only"""
+        self._need()
+        capi.check(self._lib.fx_deposit_particles(self._ctx, stream), "DepositParticles")
+
+    def ParticleDensity(self, stream=None):
+        """the scatter alone (fx_particle_density; blocks): numpy uint64 [Z][Y][X], 2^24 per live particle spread tri-linearly"""
+        self._need()
+        X, Y, Z = self.grid
+        out = np.empty((Z, Y, X), np.uint64)
+        capi.check(self._lib.fx_particle_density(self._ctx, stream, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "ParticleDensity")
+        return out
+
     def SampleVelocity(self, points, stream=None, out=None):
         """the velocity at points of texture space (fx_sample_velocity): `points` (n, 3) or (n, 4) (a fourth column is ignored) as anything numpy
         takes -> float32 (n, 3), blocking; or a float32 torch tensor (n, 4) on the context's device with `out` a float32 tensor (n, 3) there:

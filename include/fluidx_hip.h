@@ -612,7 +612,8 @@ int fx_heat(fx_ctx* ctx, void* stream);
  * the getters succeed there and report the empty default, as fx_get_emitters does.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts.  FX_E_NOMEM:
  * the buffer cannot be allocated.
  * Out of scope: spawning on the device; drawing
- * particles in the library's renders; two-way coupling; sampling colour or temperature at points. */
+ * particles in the library's renders; momentum deposit, i.e. drag back on the flow (smoke and heat the particles do leave behind:
+ * fx_set_particle_trail below); sampling colour or temperature at points. */
 #define FX_MAX_PARTICLES      (1u << 26)
 #define FX_PARTICLES_DEVICE   0x1u      /* the pointer(s) are device memory of the context's device */
 #define FX_PARTICLE_EULER     0u
@@ -680,6 +681,56 @@ int fx_get_particle_sort(fx_ctx* ctx, fx_particle_sort* out);
 int fx_sort_particles(fx_ctx* ctx, void* stream);
 int fx_particle_sort_info(fx_ctx* ctx, void* stream, struct fx_particle_sort_info* out);
 int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32);
+
+/* The particle trail (no reference counterpart): the particles as a source of smoke and heat.  While a trail is set, every live record spreads
+ * one unit of "amount" tri-linearly over the eight cells around it, and COLOR (and TEMPERATURE while fx_set_buoyancy is on) grow by that amount
+ * times the rates below: an ember leaves a smoke trail and warms the air it flies through.  A scatter from points into the grid, made
+ * reproducible the way the voxeliser is (fx_voxelize.hip): the scattered operation is an integer add, commutative and exact, so any order
+ * gives the same bits; the integers become floats once per cell.  Two launches (fx_particle_trail.hip): k_trail_splat over the records,
+ * k_trail_apply over the grid.  Off by default: a context that never calls the setter launches, computes and counts what it did before.
+ * The rule, fp32, every operation rounded as written (tests/particle_trail_ref.py restates it in numpy); N = (X, Y, Z),
+ * c(v) = fminf(fmaxf(v, 0), 1), dt = the time step of the last fx_update_frame:
+ *   scatter  a record deposits iff age >= 0 (the move's test: -0.0 is live, a NaN is dead).  Per axis a of a live record:
+ *            s = c(p_a), t = s * N_a - 0.5, fl = floor(t), f = t - fl;  q = (int)rintf(f * 256), in 0 ... 256;
+ *            the taps are (int)fl and (int)fl + 1, both clamped to [0, N_a - 1] -- the two cells the sampler U(p) reads -- with the integer
+ *            weights 256 - q and q.  A 2-D grid does not look at z: one tap, plane 0, weight 256.
+ *            The cell of each of the eight tap combinations grows by w_x * w_y * w_z in a uint64 accumulator (adds of 0 may be skipped; two
+ *            taps that clamp onto the same wall cell both add to it).  So every live record adds exactly 2^24 in total, wherever it is and
+ *            whatever its coordinates hold: a NaN or an infinity lands where the clamp says, no value reaches an index unclamped
+ *   apply    for a cell with acc != 0: if the obstacle code says the cell itself is solid (bit 6, the bit the move tests) nothing is added;
+ *            otherwise A = (float)acc * 0x1p-24f (one round-to-nearest-even conversion of the 64-bit integer, then an exact scaling),
+ *            g = rate * dt, colour_ch = fma(A, tint_ch * g, colour_ch) on the current colour field for each of the four channels, and, while
+ *            buoyancy is on and heat != 0, T = fma(A, heat * dt, T) on the current temperature, in place.  fp16 storage widens on load and
+ *            rounds once on store.  Either way the accumulator word goes back to 0: the volume is all zero between calls.  A cell with
+ *            acc == 0 is not stored: its bits, a -0 included, stay
+ * fx_set_particle_trail with a struct allocates the accumulator, one uint64 per cell (X * Y * Z * 8 bytes), zeroed; FX_E_NOMEM if that fails,
+ * the previous state staying in force.  NULL = off (the default), which frees it.  All allocation and waiting happens here:
+ * fx_deposit_particles and the step only enqueue (a captured fx_simulate stays capturable).
+ * fx_simulate runs the stage between the buoyancy pass and the obstacles' enforce pass when a trail is set, a set of particles exists and the
+ * time step is > 0, on the positions as they are then (moved at the end of the previous step, or set by the caller): colour and temperature
+ * are final for the step there, and heat left now lifts from the next step on.  Timing: booked into fx_timing.advect_ms, like its
+ * neighbours.  fx_deposit_particles is that stage alone; FX_OK and nothing done with no set or dt <= 0.
+ * fx_particle_density is the inspection call (as fx_download_pressure_level is for the multigrid): it runs the scatter alone on the set in
+ * force, copies the accumulator to out = uint64[Z][Y][X], clears it and blocks.  With no set: zeros.  It is also the particle density for a
+ * caller's own use: out / 2^24 = particles per cell, tri-linearly spread.
+ * fx_get_particle_trail: the setting in force; off reports rate 0, tint 0, heat 0.
+ * Configuration on the emitters' terms: per context, kept across fx_update_frame, not checkpointed, not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx or out-pointer, a wrong struct_size, unknown flag bits, a non-finite member,
+ * rate < 0, bytes != X * Y * Z * 8, and (all but fx_get_particle_trail, which reports the default there) slab ranks.  FX_E_STATE:
+ * FX_FLAG_RENDER_ONLY contexts; fx_deposit_particles and fx_particle_density while no trail is set.  FX_E_NOMEM: the accumulator cannot be
+ * allocated.
+ * Out of scope: per-particle strength or fading by age (the record has no room for it); momentum deposit; spawning; drawing; slab contexts;
+ * restricting the apply pass to the set's bounding box; checkpointing. */
+typedef struct fx_particle_trail {
+	uint32_t struct_size, flags;   /* sizeof(fx_particle_trail) = 32; flags: 0 */
+	float rate;                    /* amount per second and particle; finite, >= 0 */
+	float tint[4];                 /* rgba added per unit amount; finite */
+	float heat;                    /* temperature added per unit amount and second; finite, either sign */
+} fx_particle_trail;
+int fx_set_particle_trail(fx_ctx* ctx, const fx_particle_trail* trail);
+int fx_get_particle_trail(fx_ctx* ctx, fx_particle_trail* out);
+int fx_deposit_particles(fx_ctx* ctx, void* stream);
+int fx_particle_density(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes);
 
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
