@@ -149,7 +149,10 @@ int fx_set_max_samples(fx_ctx* ctx, uint32_t max_ray_samples, uint32_t max_light
 /* Fluid::SetSH (Fluid.cpp:278-281): 9 x float3 host coefficients, NULL detaches the probe */
 int fx_set_sh(fx_ctx* ctx, const float* coeffs27);
 /* Fluid::UpdateFrame (Fluid.cpp:283-346); matrices row-major, row-vector convention (DirectXMath).
- * view/proj/eye may be NULL for a pure simulation context (no rendering state is updated). */
+ * view/proj/eye may be NULL for a pure simulation context (no rendering state is updated).
+ * A call with time_step > 0 flips the colour parity (Fluid.cpp:345): from then on FX_FIELD_COLOR names the buffer the coming fx_simulate
+ * writes, and FX_FIELD_COLOR_PREV the buffer FX_FIELD_COLOR named before the call, which is the one that step's advection samples.
+ * frame_index picks one of the FX_FRAME_COUNT per-frame constant slots and enters no arithmetic of the step. */
 int fx_update_frame(fx_ctx* ctx, float time_step, uint8_t frame_index,
 	const float view[16], const float proj[16], const float eye[3]);
 /* Fluid::Simulate (Fluid.cpp:348-410): enqueues advect + divergence + N sweeps + project.  Asynchronous like the reference's call, with one
@@ -157,7 +160,23 @@ int fx_update_frame(fx_ctx* ctx, float time_step, uint8_t frame_index,
  * left in host-visible memory and waits for THAT launch's event first (hipEventSynchronize; long past in practice) -- so the host runs at
  * most about two steps ahead of the device there, and such a context must not be stepped inside a stream capture.  The wait is what makes
  * the launch sequence a function of (the last uploaded state, the steps since) instead of when the host happened to look; fx_upload of a
- * simulation field starts that adaptation over. */
+ * simulation field starts that adaptation over.
+ * The whole step with every optional stage, in order, and what each stage reads at its point of the step (each block below gives its own
+ * rule; time_step > 0, tests/step_ref.py composes the per-stage models in exactly this order and tests/test_gpu_step_model.py holds
+ * fx_simulate to it):
+ *   advect (either scheme)   traces with VELOCITY, samples VELOCITY and COLOR_PREV                          -> VELOCITY1, COLOR
+ *   inflow                   the advection's back-trace again: VELOCITY                                     -> COLOR in place
+ *   emit                                                                                                    -> VELOCITY1, COLOR in place
+ *   heat                     traces TEMPERATURE with VELOCITY; rho = COLOR.w as the stages above left it    -> TEMPERATURE (the two buffers
+ *                            swap: every later stage and the next step see the new field), VELOCITY1 in place
+ *   trail                    the particle positions as the buffer holds them now                            -> COLOR, TEMPERATURE in place
+ *   enforce                                                                                                 -> VELOCITY1, COLOR in place
+ *   confine                  VELOCITY1                                                                      -> VELOCITY1 (the names swap)
+ *   divergence               VELOCITY1                                                                      -> DIVERGENCE
+ *   solve                    DIVERGENCE, PRESSURE as the previous step (or an upload) left it               -> PRESSURE
+ *   project                  VELOCITY1, PRESSURE                                                            -> VELOCITY
+ *   particles                the sort when this run of the stage is due one, then the move through the VELOCITY just projected
+ * Behind the step FX_FIELD_VELOCITY1 holds what the divergence read, FX_FIELD_COLOR_PREV what the advection sampled. */
 int fx_simulate(fx_ctx* ctx, void* stream, uint8_t frame_index);
 /* Fluid::Render (Fluid.cpp:412-446), all four flag combinations:
  *   flags & FX_RAY_MARCH_CUBEMAP   cube-map-space march (merged, or light volume + view pass with FX_SEPARATE_LIGHT_PASS):

@@ -232,3 +232,18 @@ def threshold_counts(dims):
     widest = max(planner(cells, 1)["digit_bits"])
     wgs = k["scan_tile"] // (1 << widest) + 1                             # the first workgroup count whose (1 << widest) * wgs passes one tile
     return [k["records"] - 1, k["records"], k["records"] + 1, (wgs - 1) * k["records"] + 1]
+
+
+SCAN_ROUND_EXTRA = 4                                                      # block sums the second round holds at the least: more than one
+
+
+def scan_round_counts(dims):
+    """k_psort_scan_sums scans the block sums in rounds of one per thread and carries a running total from round to round: -> [the largest count
+    whose widest pass still has `threads` scan blocks, the last single round; the first count with threads + SCAN_ROUND_EXTRA of them]"""
+    k = constants()
+    cells = dims[0] * dims[1] * dims[2]
+    widest = max(planner(cells, 1)["digit_bits"])
+    last_single = (k["threads"] * k["scan_tile"]) >> widest               # workgroups: (wgs << widest) entries fill `threads` tiles exactly
+    blocks = k["threads"] + SCAN_ROUND_EXTRA
+    first_wgs = -(-((blocks - 1) * k["scan_tile"] + 1) // (1 << widest))    # the first workgroup count whose entries reach into tile `blocks`
+    return [last_single * k["records"], (first_wgs - 1) * k["records"] + 1]

@@ -2,7 +2,8 @@
 cases the reference's defaults hit; these draw grid extents, storage, addressing, sweep counts / modes, fusion, slab cuts,
 halo widths and schedules at random (fixed seeds, so a failure reproduces) and hold the same bars:
   * one full step from a random state: HIP vs oracle (bit-exact where no transcendental is on the path);
-  * random z-slab decompositions vs the single-domain HIP run: bit-identical."""
+  * random z-slab decompositions vs the single-domain HIP run: bit-identical.
+No optional setter is called here: the trajectories of the optional stages are held by tests/test_gpu_step_model.py against tests/step_ref.py."""
 import os
 
 import numpy as np

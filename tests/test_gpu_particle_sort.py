@@ -4,7 +4,8 @@ tests/particle_sort_ref.py: the sorted buffer, order and live, everything compar
 Shapes: particle_ref.SHAPES -- keys of 11 to 19 bits, two and three passes -- and (3, 3, 2), one pass of 5 bits (it stands in for (5, 3, 2), which
 no context can hold: fx_create takes X == Y only; the model and the planner are tested on (5, 3, 2) itself).  Counts: 1, 2, 255, 256, 257, 4099, 65 537,
 2^18 + 1, and what the planner says its own edges are: one below, at and one above the records of a workgroup, and the first count whose histogram
-takes a second scan block.  The sort reads no field, so both storages are run on one shape only."""
+takes a second scan block; on (70, 70, 5) also the last count whose block sums are scanned in one round and one that needs a second (a little
+over two million records).  The sort reads no field, so both storages are run on one shape only."""
 import ctypes as C
 import functools
 
@@ -73,6 +74,21 @@ def test_every_arrangement_sorts_as_the_model_does(dims, storage):
                 assert live == n
             if name in ("one_cell", "sorted"):
                 assert np.array_equal(order, np.arange(n, dtype=np.uint32))
+    f.Release()
+
+
+@pytest.mark.parametrize("name", ["random", "two_cells", "live_dead"])
+@pytest.mark.parametrize("which", [0, 1], ids=["last_single_round", "second_round"])
+def test_the_scan_of_the_block_sums_carries_into_a_second_round(which, name):
+    """(70, 70, 5): digits of 8 + 7 bits.  The largest count whose 8-bit pass has 256 scan blocks, one round of k_psort_scan_sums, and a count
+    with 260: the running total crosses into a second round that holds more than one entry (tests/test_particle_sort_ref.py holds the planner
+    to both figures).  A little over two million records each."""
+    dims = (70, 70, 5)
+    n = ps.scan_round_counts(dims)[which]
+    f = make(dims)
+    f.SetParticleSort(True)
+    _, order, live = sort_and_check(f, ps.arrangement(name, dims, n, seed=31), dims, (name, n))
+    assert 0 < live <= n and not np.array_equal(order, np.arange(n, dtype=np.uint32))
     f.Release()
 
 

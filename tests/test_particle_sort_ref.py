@@ -188,3 +188,20 @@ def test_the_thresholds_the_gpu_tests_read():
         assert (ps.planner(cells, below)["wgs"], ps.planner(cells, at)["wgs"], ps.planner(cells, above)["wgs"]) == (1, 1, 2)
         assert max(ps.planner(cells, second - 1)["scan_blocks"]) == 1 and max(ps.planner(cells, second)["scan_blocks"]) == 2
     assert k["records"] >= 256 and k["scan_tile"] >= 256
+
+
+def test_the_counts_that_reach_a_second_round_of_block_sums():
+    """tests/test_gpu_particle_sort.py sorts these two on (70, 70, 5): 15 key bits as digits of 8 + 7, the widest digit the kernels have"""
+    k = ps.constants()
+    dims = (70, 70, 5)
+    cells = dims[0] * dims[1] * dims[2]
+    assert ps.planner(cells, 1)["digit_bits"] == [8, 7] and k["max_digit_bits"] == 8
+    single, second = ps.scan_round_counts(dims)
+    assert max(ps.planner(cells, single)["scan_blocks"]) == k["threads"] == 256              # the last single round ...
+    assert max(ps.planner(cells, single + 1)["scan_blocks"]) == k["threads"] + 1             # ... one record more starts the second
+    assert max(ps.planner(cells, second)["scan_blocks"]) == 260 and max(ps.planner(cells, second - 1)["scan_blocks"]) == 259
+    assert 2_000_000 < single < second < 2_200_000 <= k["max_count"]
+    # no count the GPU tests sorted so far gets there, on any of their grids
+    for d in ps.SHAPES + ps.GPU_SHAPES:
+        for n in ps.COUNTS + ps.threshold_counts(d):
+            assert max(ps.planner(d[0] * d[1] * d[2], n)["scan_blocks"]) <= k["threads"], (d, n)
