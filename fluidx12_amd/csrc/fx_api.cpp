@@ -533,7 +533,7 @@ int fx_get_obstacles(fx_ctx* ctx, uint8_t* solid_out, size_t bytes, uint64_t* so
 
 int fx_enforce_obstacles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, enforce_phase); }
 
-// ---- the solids' rigid-body velocities (fx_obstacle_moving.hip): a host-side list like the emitters ---------------------------------
+// ---- the solids' rigid-body velocities (fx_obstacle.hip): a host-side list like the emitters ---------------------------------
 int fx_set_obstacle_bodies(fx_ctx* ctx, const fx_obstacle_body* list, uint32_t count)
 {
 	if (const int rc = sim_guard(ctx)) return rc;

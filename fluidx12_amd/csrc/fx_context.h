@@ -70,7 +70,7 @@ struct fx_ctx {
 	uint64_t obst_cells = 0;        // solid cells
 	int obst_lo[3] = { 0, 0, 0 }, obst_hi[3] = { 0, 0, 0 };   // their bounding box [lo, hi): what the enforce launch covers
 	// the solids' rigid-body velocities (fx_set_obstacle_bodies; configuration on the same terms): a solid cell belongs to the first body whose
-	// box holds its centre.  In force while obst_code is set and the list is not empty: the moving kernels (fx_obstacle_moving.hip) then run
+	// box holds its centre.  In force while obst_code is set and the list is not empty: the obstacle kernels (fx_obstacle.hip) then get it
 	std::vector<fx_obstacle_body> obst_bodies;   // may be set with no mask in force; empty = every solid rests (default)
 	// the mesh voxeliser's scratch (fx_set_obstacle_meshes, fx_voxelize.hip), allocated by the first call: nothing in it outlives a call
 	unsigned* vox_bits = nullptr;   // the toggle bitmap, [Z][Y][X / 32 + 1] words; all zero between calls (the fill kernel clears what it reads)

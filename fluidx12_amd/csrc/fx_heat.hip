@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_heat(const Geom g, const HeatArgs a, co
 	}
 
 	// ---- 4, 5: a solid cell holds the ambient value and keeps its velocity bits
-	const bool solid = code != nullptr && (code[id] & 64u) != 0;
+	const bool solid = code != nullptr && (code[id] & OB_SELF) != 0;
 	if (solid) T1 = Ta;
 	*reinterpret_cast<float*>(reinterpret_cast<char*>(t_out) + id * (O)4) = T1;
 	if (solid) return;

@@ -165,32 +165,27 @@ hipError_t launch_open_inflow(const Geom& g, int half_store, const void* vel0, v
 hipError_t launch_divergence(const Geom& g, int half_store, const void* vel, float* b, int z_begin, int z_end, hipStream_t s);
 // ---- solid obstacles (fx_obstacle.hip), whole grids only (hipErrorNotSupported for a slab geometry).  code: one byte per cell, bits 0..5 = the
 // clamped neighbour at x-1, x+1, y-1, y+1, z-1, z+1 is solid (z bits 0 on 2-D grids), bit 6 = the cell is; the stencil launchers read it, never the mask
+enum { OB_XM = 1, OB_XP = 2, OB_YM = 4, OB_YP = 8, OB_ZM = 16, OB_ZP = 32, OB_SELF = 64 };
 // launch_obstacle_codes: solid_dev uint8[Z][Y][X] (device) -> code; stats_dev (8 device words) gets { solid cells (2 words, low first), min x, y, z, max x, y, z }
 hipError_t launch_obstacle_codes(const Geom& g, const uint8_t* solid_dev, uint8_t* code, unsigned* stats_dev, hipStream_t s);
 hipError_t launch_obstacle_mask(const uint8_t* code, uint8_t* solid_dev, size_t n, hipStream_t s);      // the 0 / 1 mask back out of the codes
 // the enforce launch's tiles: the solids' box [lo, hi) on the grid's 64 x 4 raster, first tile at (*x0, *y0, lo[2]) -> workgroups (host code)
 long long obstacle_enforce_tiles(const int lo[3], const int hi[3], int* x0, int* y0, int* tiles_x, int* tiles_y);
-// solid cells of vel (3 components) / col become +0, in place; alpha: the render's side volume when it holds this colour field's alpha, else null
-hipError_t launch_obstacle_enforce(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3], void* vel, void* col,
-	float* alpha, hipStream_t s);
-hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel, const uint8_t* code, float* b, int z_begin, int z_end, hipStream_t s);
+// The three launches whose rule sees the solid's velocity take the bodies of fx_set_obstacle_bodies: (list, count) with count == 0 = the solids
+// rest, count >= 1 = a solid cell moves with the first body whose box holds its centre (then code must not be null and count no more than
+// FX_MAX_OBSTACLE_BODIES: else hipErrorInvalidValue).  The sweeps never see the bodies.
+// solid cells of vel (3 components) become their body's velocity (+0 at rest), those of col +0, in place; alpha: the render's side volume when it
+// holds this colour field's alpha, else null
+hipError_t launch_obstacle_enforce(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3],
+	const fx_obstacle_body* list, int count, void* vel, void* col, float* alpha, hipStream_t s);
+hipError_t launch_divergence_obs(const Geom& g, int half_store, const void* vel, const uint8_t* code, const fx_obstacle_body* list, int count,
+	float* b, int z_begin, int z_end, hipStream_t s);
 // the boundary-aware sweep (one per launch; 3-D, X % 4 == 0: four cells per thread, else the scalar kernel) and projection, for obstacles,
 // open walls or both.  code: the obstacle bytes, or null (then no code byte is read); faces: the open walls' FX_WALL_* bits, or 0 (all closed);
 // neither: hipErrorInvalidValue, that is the plain kernels' case
 hipError_t launch_jacobi_bnd(const Geom& g, const float* p_in, const float* b, const uint8_t* code, float* p_out, unsigned faces,
 	int z_begin, int z_end, hipStream_t s);
 hipError_t launch_project_bnd(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
-	void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
-// ---- solids that move (fx_obstacle_moving.hip; fx_set_obstacle_bodies), whole grids only: the three obstacle launches whose rule sees the
-// solid's velocity, taken while a mask is in force and the list is not empty (count >= 1, code not null: else hipErrorInvalidValue).  The
-// sweeps are launch_jacobi_bnd's either way.  BodyArgs is what the kernels get: the list by value, and whether the grid is 3-D
-struct BodyArg { float lo[3], hi[3], lin[3], ang[3], piv[3]; };
-struct BodyArgs { int n, is3d; BodyArg b[FX_MAX_OBSTACLE_BODIES]; };
-hipError_t launch_obstacle_enforce_mov(const Geom& g, int half_store, const uint8_t* code, const int lo[3], const int hi[3],
-	const fx_obstacle_body* list, int count, void* vel, void* col, float* alpha, hipStream_t s);
-hipError_t launch_divergence_obs_mov(const Geom& g, int half_store, const void* vel, const uint8_t* code, const fx_obstacle_body* list, int count,
-	float* b, int z_begin, int z_end, hipStream_t s);
-hipError_t launch_project_bnd_mov(const Geom& g, const SimParams& sp, int half_store, const void* vel_in, const float* p, const uint8_t* code,
 	const fx_obstacle_body* list, int count, void* vel_out, unsigned faces, int z_begin, int z_end, hipStream_t s);
 // ---- the mesh voxeliser (fx_voxelize.hip; fx_set_obstacle_meshes), whole 3-D grids only: closed triangle meshes -> the 0 / 1 byte mask
 // launch_obstacle_codes reads.  The rule is integer arithmetic on coordinates quantised to 1 / 256 of a cell (include/fluidx_hip.h).

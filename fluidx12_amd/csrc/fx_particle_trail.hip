@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void k_trail_apply(const Geom g, const TrailAr
 	const u64 v = *word;
 	if (v == 0) return;                                                 // no particle near: the cell keeps its bits
 	*word = 0;
-	if (code != nullptr && (code[id] & 64u) != 0) return;               // a solid cell takes nothing
+	if (code != nullptr && (code[id] & OB_SELF) != 0) return;               // a solid cell takes nothing
 	const float A = (float)v * 0x1p-24f;
 	const float gdt = a.rate * a.dt;
 	char* co = static_cast<char*>(col);

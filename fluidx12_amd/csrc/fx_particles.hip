@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_move_particles(const Geom geo, const Pa
 		const int cx = cell_axis(qx, g.X), cy = cell_axis(qy, g.Y);
 		const int cz = IS3D ? cell_axis(qz, g.Z) : 0;
 		const size_t cell = ((size_t)cz * (size_t)g.Y + (size_t)cy) * (size_t)g.X + (size_t)cx;
-		if (code[cell] & 64u) { qx = r.x; qy = r.y; qz = r.z; }
+		if (code[cell] & OB_SELF) { qx = r.x; qy = r.y; qz = r.z; }
 	}
 	const float age1 = r.w + dt;
 	if (a.lifetime > 0.0f && age1 >= a.lifetime) dead = true;

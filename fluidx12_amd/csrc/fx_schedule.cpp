@@ -389,19 +389,15 @@ int trail_splat_phase(fx_ctx* ctx, hipStream_t s)
 // Solid obstacles (fx_obstacle.hip): behind the advection and the emitters, in front of the confinement, the solid cells of the advected velocity
 // and colour become +0, in place -- one launch over the solids' bounding box, booked with the advection like the two passes around it.  When this
 // step's advection left the alpha of colour[parity] in the render's side volume, the pass keeps that volume true as well (the emitters' condition).
-// While the solids have bodies (fx_set_obstacle_bodies, fx_obstacle_moving.hip) this pass, the divergence and the projection take their moving
-// variants: the velocity of a solid cell is its body's, not +0.  An empty list: the launches below are the ones they were.
+// While the solids have bodies (fx_set_obstacle_bodies) this pass, the divergence and the projection get the list: the velocity of a solid cell
+// is its body's, not +0.  An empty list: the launches below are the ones they were.
 int enforce_phase(fx_ctx* ctx, hipStream_t s)
 {
 	if (!ctx->obst_code || !ctx->obst_cells || !(ctx->time_step > 0.0f)) return FX_OK;
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_ADVECT);
-	if (!ctx->obst_bodies.empty()) {                                // the solids move (fx_obstacle_moving.hip): their cells get the body's velocity
-		FX_HIP(launch_obstacle_enforce_mov(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->obst_bodies.data(), (int)ctx->obst_bodies.size(),
-			ctx->vel[1], ctx->col[ctx->frame_parity], alpha_mirror(ctx), s));
-		return FX_OK;
-	}
-	FX_HIP(launch_obstacle_enforce(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->vel[1], ctx->col[ctx->frame_parity], alpha_mirror(ctx), s));
+	FX_HIP(launch_obstacle_enforce(ctx->g, ctx->half, ctx->obst_code, ctx->obst_lo, ctx->obst_hi, ctx->obst_bodies.data(), (int)ctx->obst_bodies.size(),
+		ctx->vel[1], ctx->col[ctx->frame_parity], alpha_mirror(ctx), s));
 	return FX_OK;
 }
 
@@ -410,12 +406,8 @@ int divergence_phase(fx_ctx* ctx, hipStream_t s)
 	DeviceGuard dg(ctx->device);
 	ScopedMark mk(ctx, s, MK_DIV);
 	const Range r = owned(ctx);
-	if (ctx->obst_code && !ctx->obst_bodies.empty()) {
-		FX_HIP(launch_divergence_obs_mov(ctx->g, ctx->half, ctx->vel[1], ctx->obst_code, ctx->obst_bodies.data(), (int)ctx->obst_bodies.size(), ctx->b, r.lo, r.hi, s));
-		return FX_OK;
-	}
 	if (ctx->obst_code) {
-		FX_HIP(launch_divergence_obs(ctx->g, ctx->half, ctx->vel[1], ctx->obst_code, ctx->b, r.lo, r.hi, s));
+		FX_HIP(launch_divergence_obs(ctx->g, ctx->half, ctx->vel[1], ctx->obst_code, ctx->obst_bodies.data(), (int)ctx->obst_bodies.size(), ctx->b, r.lo, r.hi, s));
 		return FX_OK;
 	}
 	FX_HIP(launch_divergence(ctx->g, ctx->half, ctx->vel[1], ctx->b, r.lo, r.hi, s));
@@ -823,13 +815,10 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 	const Range r = owned(ctx);
 	int* rec = multi_rank(ctx) ? ctx->step_rec : nullptr;           // slab ranks: the projection also measures the next advection's need
 	ctx->rec_in_project = false;
-	if (ctx->obst_code && !ctx->obst_bodies.empty()) {              // moving solids, with or without open walls
-		FX_HIP(launch_project_bnd_mov(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->obst_bodies.data(), (int)ctx->obst_bodies.size(),
+	if (ctx->obst_code || ctx->open_faces) {                        // obstacles (resting or moving), open walls or both: the boundary-aware projection
+		const int bodies = ctx->obst_code ? (int)ctx->obst_bodies.size() : 0;       // without a mask the list is idle
+		FX_HIP(launch_project_bnd(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->obst_bodies.data(), bodies,
 			ctx->vel[0], ctx->open_faces, r.lo, r.hi, s));
-		return FX_OK;
-	}
-	if (ctx->obst_code || ctx->open_faces) {                        // obstacles, open walls or both: the boundary-aware projection
-		FX_HIP(launch_project_bnd(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->obst_code, ctx->vel[0], ctx->open_faces, r.lo, r.hi, s));
 		return FX_OK;
 	}
 	FX_HIP(launch_project(ctx->g, sp, ctx->half, ctx->vel[1], ctx->p[ctx->p_cur], ctx->vel[0], r.lo, r.hi, s,

@@ -1,4 +1,4 @@
-"""numpy model of the moving obstacles (include/fluidx_hip.h fx_set_obstacle_bodies, fluidx12_amd/csrc/fx_obstacle_moving.hip): the rules in
+"""numpy model of the moving obstacles (include/fluidx_hip.h fx_set_obstacle_bodies, fluidx12_amd/csrc/fx_obstacle.hip): the rules in
 fp32, every operation rounded as written.
 
   wall_velocity   w(n) = linear + angular x r of every cell as if it were solid: the first body whose closed box holds the cell centre, +0 if none

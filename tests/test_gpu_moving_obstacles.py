@@ -1,9 +1,9 @@
-"""Moving obstacles on the GPU (fx_set_obstacle_bodies / fx_get_obstacle_bodies, csrc/fx_obstacle_moving.hip).
+"""Moving obstacles on the GPU (fx_set_obstacle_bodies / fx_get_obstacle_bodies, csrc/fx_obstacle.hip).
 
 Every comparison is bit for bit against the numpy model tests/moving_obstacle_ref.py (tests/test_moving_obstacle_ref.py anchors it to the
 resting obstacles' reference): the three stages that see the bodies and the sweeps between them, with closed walls and with two open ones;
 fx_simulate against the stage calls and against the model's step; bodies that hold no solid cell and an empty list against a context that
-never heard of the call; a ball that is voxelised anew every frame.  The model's step starts behind the stages the bodies do not touch
+never heard of the call; bodies that stand still against the empty list; a ball that is voxelised anew every frame.  The model's step starts behind the stages the bodies do not touch
 (advection, inflow, emitters, buoyancy, confinement): those run on the device, and what they leave is what the model continues from.
 
 Shapes (X = Y, Z): (20, 5) a row shorter than a tile, (36, 1) 2-D, (68, 5) X % 64 != 0 with the wide sweep, (64, 8) the wide sweep on full
@@ -221,11 +221,12 @@ def test_simulate_is_the_stage_composition_and_the_model_s_step(dims, storage, v
 
 
 # ---- 3: equivalence -----------------------------------------------------------------------------------------------------------------------------
-def run_plain(dims, storage, mask, bodies, call=True, steps=3, timing=False):
+def run_plain(dims, storage, mask, bodies, call=True, steps=3, timing=False, faces=0):
     vel, col, _ = rand_state(dims, 613, storage == "fp16", scale=0.2)
     f = make(dims, storage=storage, jacobi_iters=8)
     f.upload(fx.FIELD_VELOCITY, vel); f.upload(fx.FIELD_COLOR, col)
     f.SetObstacles(mask)
+    f.SetOpenWalls(faces)
     if call:
         f.SetObstacleBodies(bodies)
     f.timing_enable(True)
@@ -273,6 +274,22 @@ def test_at_rest_the_context_runs_what_it_ran_before(dims, storage):
     t = f.timing_read()
     assert ([f.digest(k) for k in ALL_FIELDS], (t.steps, t.jacobi_launches, t.jacobi_sweeps, t.jacobi_main_launches, t.jacobi_main_sweeps)) == never
     f.Release()
+
+
+@pytest.mark.parametrize("dims,storage,faces", [(d, s, 0) for d in [(20, 20, 5), (36, 36, 1), (64, 64, 8)] for s in ("fp32", "fp16")]
+                         + [((64, 64, 8), s, OPEN) for s in ("fp32", "fp16")])
+def test_bodies_that_stand_still_give_the_resting_bits(dims, storage, faces):
+    """What lets one kernel body serve the resting and the moving solids: the scene's bodies, boxes and pivots kept, with linear = angular =
+    +0 run the MOV = 1 kernels over every solid cell and must leave all six fields as the empty list (MOV = 0) leaves them, bit for bit.
+    r = pos - pivot takes both signs along x and y over the solid cells the bodies hold; fmaf(-0, r, +0) is +0 either way."""
+    m, bodies = scene(dims)
+    still = [mv.body(b["box_lo"], b["box_hi"], pivot=b["pivot"]) for b in bodies]
+    assert all(b["linear"] == (0.0, 0.0, 0.0) and b["angular"] == (0.0, 0.0, 0.0) and not np.signbit(b["linear"] + b["angular"]).any() for b in still)
+    who, pos = mv.body_of(m.shape, still), mv.cell_centres(m.shape)
+    for a in range(2):
+        r = np.concatenate([pos[a][(who == k) & m.astype(bool)] - f32(b["pivot"][a]) for k, b in enumerate(still)])
+        assert (r < 0).any() and (r > 0).any(), a
+    assert run_plain(dims, storage, m, still, faces=faces)[0] == run_plain(dims, storage, m, [], faces=faces)[0]
 
 
 # ---- 4: a moving mask -----------------------------------------------------------------------------------------------------------------------

@@ -214,7 +214,7 @@ def test_mirrors_carry_the_two_calls():
     for name in ("SetObstacleBodies", "GetObstacleBodies", "fx_set_obstacle_bodies", "fx_get_obstacle_bodies"):
         assert name in hpp, name
     from fluidx12_amd import build
-    assert "fx_obstacle_moving.hip" in build.SOURCES
+    assert "fx_obstacle.hip" in build.SOURCES and "fx_obstacle_moving.hip" not in build.SOURCES      # one file holds the resting and the moving rules
     demo = open(os.path.join(ROOT, "examples", "fluidx_demo.cpp")).read()
     assert "-obstacleVelocity" in demo and "SetObstacleBodies" in demo
 

@@ -1,11 +1,11 @@
-"""What moving obstacles cost (fx_set_obstacle_bodies; csrc/fx_obstacle_moving.hip): a table for docs/LAB.md, not a figure of bench.py.
+"""What moving obstacles cost (fx_set_obstacle_bodies; csrc/fx_obstacle.hip): a table for docs/LAB.md, not a figure of bench.py.
 
     python tools/moving_obstacle_bench.py [--grid 256] [--iters 40] [--steps 100] [--warmup 20] [--repeats 3] [--storage fp32] [--resting-only] [--json out.json]
 
 One process, two contexts on one grid with the ball of tests/test_obstacle_ref.py `ball_mask` (centre (0.5, 0.45, 0.5), radius 0.22) as the
 mask, stepped in turn so that both legs see the same device state; the times are the device events of fx_timing.  Legs:
-  R  the ball at rest (no bodies): k_obstacle_enforce, k_divergence_obs, k_project_bnd -- the launches of a library without the call
-  M  one translating body whose box encloses the ball: the three _mov kernels; the sweeps are the same k_jacobi_bnd_v4 launches
+  R  the ball at rest (no bodies): k_obstacle_enforce, k_divergence_obs, k_project_bnd with MOV = 0 -- the launches of a library without the call
+  M  one translating body whose box encloses the ball: the same three with MOV = 1; the sweeps are the same k_jacobi_bnd_v4 launches
 Every repeat prints one line per leg: the step in ms and its split (advect_ms holds the enforce pass).  --resting-only runs leg R alone and
 also takes a library that predates the call (FLUIDX_LIB_PATH=...): the resting figure of an older build, for the comparison across commits.
 """
