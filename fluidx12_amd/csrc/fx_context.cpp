@@ -57,14 +57,7 @@ int drain_timing(fx_ctx* c)
 }
 
 // ---- staging ----------------------------------------------------------------------------------
-int ensure_stage(fx_ctx* ctx, size_t bytes)
-{
-	if (ctx->stage_bytes >= bytes) return FX_OK;
-	if (ctx->stage) { FX_HIP(hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-	FX_HIP(hipMalloc((void**)&ctx->stage, bytes));
-	ctx->stage_bytes = bytes;
-	return FX_OK;
-}
+int ensure_stage(fx_ctx* ctx, size_t bytes) { return dev_grow(ctx, &ctx->stage, &ctx->stage_bytes, bytes); }
 
 void destroy_lanes(fx_comm_group* g)
 {
@@ -170,86 +163,58 @@ int fx_create(fx_ctx** out, const fx_desc* d)
 	int rc = [&]() -> int {
 		FX_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
 		ctx->owns_stream = true;
-		const size_t cells = ctx->g.cells_local();
-		const size_t es = elem_size(ctx);
-		if (d->flags & FX_FLAG_RENDER_ONLY) {                                // colour only; parity never flips
-			FX_HIP(hipMalloc(&ctx->col[0], 4 * cells * es));
-			FX_HIP(hipMemsetAsync(ctx->col[0], 0, 4 * cells * es, ctx->stream));
-		}
-		for (int i = 0; i < 2 && !(d->flags & FX_FLAG_RENDER_ONLY); ++i) {
-			FX_HIP(hipMalloc(&ctx->vel[i], 3 * cells * es));
-			FX_HIP(hipMalloc(&ctx->col[i], 4 * cells * es));
-			FX_HIP(hipMalloc((void**)&ctx->p[i], cells * 4));
-			FX_HIP(hipMemsetAsync(ctx->vel[i], 0, 3 * cells * es, ctx->stream));
-			FX_HIP(hipMemsetAsync(ctx->col[i], 0, 4 * cells * es, ctx->stream));
-			FX_HIP(hipMemsetAsync(ctx->p[i], 0, cells * 4, ctx->stream));
-		}
-		if (slab && !(d->flags & FX_FLAG_RENDER_ONLY))                       // scratch levels of the face chains (jacobi_overlapped)
-			for (int i = 0; i < 2; ++i) {
-				FX_HIP(hipMalloc((void**)&ctx->p_face[i], cells * 4));
-				FX_HIP(hipMemsetAsync(ctx->p_face[i], 0, cells * 4, ctx->stream));
-			}
-		if (!(d->flags & FX_FLAG_RENDER_ONLY)) {
-			FX_HIP(hipMalloc((void**)&ctx->b, cells * 4));
-			FX_HIP(hipMemsetAsync(ctx->b, 0, cells * 4, ctx->stream));
-		}
-		if (d->jacobi_mode == FX_JACOBI_FAITHFUL && !(d->flags & FX_FLAG_RENDER_ONLY)) {
-			FX_HIP(hipMalloc((void**)&ctx->frozen, cells));
-			FX_HIP(hipMemsetAsync(ctx->frozen, 0, cells, ctx->stream));
-			if (ctx->g.Zg == 1) {                                            // 2-D: the LDS-tile kernel double-buffers the mask
-				FX_HIP(hipMalloc((void**)&ctx->frozen_alt, cells));
-				FX_HIP(hipMemsetAsync(ctx->frozen_alt, 0, cells, ctx->stream));
-			}
+		const size_t cells = ctx->g.cells_local(), es = elem_size(ctx);
+		const bool sim = !(d->flags & FX_FLAG_RENDER_ONLY);
+		int rc = FX_OK;                                                      // of the allocation that failed: zeroed / plain return true then
+		auto zeroed = [&](auto** p, size_t bytes) { return (rc = dev_alloc_zeroed(ctx, p, bytes)) != FX_OK; };      // (on the context's stream)
+		auto plain = [&](auto** p, size_t bytes) { return (rc = dev_alloc(ctx, p, bytes)) != FX_OK; };
+		if (!sim && zeroed(&ctx->col[0], 4 * cells * es)) return rc;         // colour only; parity never flips
+		for (int i = 0; i < 2 && sim; ++i)
+			if (zeroed(&ctx->vel[i], 3 * cells * es) || zeroed(&ctx->col[i], 4 * cells * es) || zeroed(&ctx->p[i], cells * 4)) return rc;
+		for (int i = 0; i < 2 && slab && sim; ++i)                           // scratch levels of the face chains (jacobi_overlapped)
+			if (zeroed(&ctx->p_face[i], cells * 4)) return rc;
+		if (sim && zeroed(&ctx->b, cells * 4)) return rc;
+		if (d->jacobi_mode == FX_JACOBI_FAITHFUL && sim) {
+			if (zeroed(&ctx->frozen, cells)) return rc;
+			if (ctx->g.Zg == 1 && zeroed(&ctx->frozen_alt, cells)) return rc;    // 2-D: the LDS-tile kernel double-buffers the mask
 			if (jacobi_freeze_supported(ctx->g)) {                           // the sparse solver of fx_jacobi_freeze.hip
 				const size_t mb = jacobi_freeze_mask_bytes(ctx->g), nt = (size_t)jacobi_freeze_tiles(ctx->g);
-				FX_HIP(hipMalloc((void**)&ctx->p_aux, cells * 4));
-				FX_HIP(hipMemsetAsync(ctx->p_aux, 0, cells * 4, ctx->stream));
-				for (int i = 0; i < 3; ++i) {
-					FX_HIP(hipMalloc((void**)&ctx->fz_mask[i], mb));
-					FX_HIP(hipMemsetAsync(ctx->fz_mask[i], 0, mb, ctx->stream));
-				}
-				FX_HIP(hipMalloc((void**)&ctx->fz_tile_next, nt * sizeof(uint32_t)));
-				FX_HIP(hipMemsetAsync(ctx->fz_tile_next, 0, nt * sizeof(uint32_t), ctx->stream));
-				for (int i = 0; i < 2; ++i) FX_HIP(hipMalloc(&ctx->fz_list[i], jacobi_freeze_list_bytes(ctx->g)));
-				FX_HIP(hipMalloc((void**)&ctx->fz_counts, 2 * jacobi_freeze_count_words() * sizeof(uint32_t)));
-				FX_HIP(hipMemsetAsync(ctx->fz_counts, 0, 2 * jacobi_freeze_count_words() * sizeof(uint32_t), ctx->stream));
-				FX_HIP(hipMalloc((void**)&ctx->fz_stat, kFreezeStatRing * sizeof(uint32_t)));
-				FX_HIP(hipMemsetAsync(ctx->fz_stat, 0, kFreezeStatRing * sizeof(uint32_t), ctx->stream));
+				if (zeroed(&ctx->p_aux, cells * 4)) return rc;
+				for (int i = 0; i < 3; ++i) if (zeroed(&ctx->fz_mask[i], mb)) return rc;
+				if (zeroed(&ctx->fz_tile_next, nt * sizeof(uint32_t))) return rc;
+				for (int i = 0; i < 2; ++i) if (plain(&ctx->fz_list[i], jacobi_freeze_list_bytes(ctx->g))) return rc;
+				if (zeroed(&ctx->fz_counts, 2 * jacobi_freeze_count_words() * sizeof(uint32_t))) return rc;
+				if (zeroed(&ctx->fz_stat, kFreezeStatRing * sizeof(uint32_t))) return rc;
 				ctx->fz_iters.assign(kFreezeStatRing, 0);
-				if (jacobi_freeze_strip_supported(ctx->g) && hipHostMalloc((void**)&ctx->fz_active_host, 64, hipHostMallocMapped) == hipSuccess) {
+				if (jacobi_freeze_strip_supported(ctx->g) && try_host_alloc(&ctx->fz_active_host, 64, hipHostMallocMapped) == hipSuccess) {   // (best effort)
 					ctx->fz_active_host[0] = 0u;
-					if (hipHostGetDevicePointer((void**)&ctx->fz_active_dev, ctx->fz_active_host, 0) != hipSuccess) ctx->fz_active_dev = nullptr;
-				} else (void)hipGetLastError();
+					if (hipHostGetDevicePointer((void**)&ctx->fz_active_dev, ctx->fz_active_host, 0) != hipSuccess) { (void)hipGetLastError(); ctx->fz_active_dev = nullptr; }
+				}
 			}
 		}
-		FX_HIP(hipMalloc((void**)&ctx->halo_overflow, sizeof(unsigned)));
-		FX_HIP(hipMemsetAsync(ctx->halo_overflow, 0, sizeof(unsigned), ctx->stream));
-		if (!(d->flags & FX_FLAG_RENDER_ONLY)) {
+		if (zeroed(&ctx->halo_overflow, sizeof(unsigned))) return rc;
+		if (sim) {
 			// scratch the staged advection puts far-tracing voxels aside in (fx_advect_lds.hip), for the owned planes: allocated here, not
 			// inside the first step (an allocation there is a device synchronisation on the step path).  Without it -- no staged path for
 			// this geometry, or no memory -- the staged kernel gathers those voxels itself.
 			ctx->adv_far_tried = true;
 			const size_t words = advect_far_words(ctx->g, ctx->g.nz);
-			if (words) {
-				if (hipMalloc((void**)&ctx->adv_far, words * sizeof(uint32_t)) == hipSuccess) {
-					FX_HIP(hipMemsetAsync(ctx->adv_far, 0, 2 * sizeof(uint32_t), ctx->stream));   // the two alternating totals
-					ctx->adv_far_words = words;
-				} else { (void)hipGetLastError(); ctx->adv_far = nullptr; }
+			if (words && try_dev_alloc(&ctx->adv_far, words * sizeof(uint32_t)) == hipSuccess) {
+				FX_HIP(hipMemsetAsync(ctx->adv_far, 0, 2 * sizeof(uint32_t), ctx->stream));   // the two alternating totals
+				ctx->adv_far_words = words;
 			}
 		}
 		if (d->grid_z > 1) {                                                 // rendering resources (Fluid.cpp:222-232)
-			FX_HIP(hipMalloc((void**)&ctx->lightmap, ctx->g.cells_owned() * 4));
-			FX_HIP(hipMemsetAsync(ctx->lightmap, 0, ctx->g.cells_owned() * 4, ctx->stream));
+			if (zeroed(&ctx->lightmap, ctx->g.cells_owned() * 4)) return rc;
 			size_t off = 0;
 			for (uint32_t m = 0; m < kNumMips; ++m) {
 				ctx->cube_mip_offset[m] = off;
 				const size_t sz = std::max<uint32_t>(d->grid_x >> m, 1);
 				off += 6 * sz * sz * 4;
 			}
-			FX_HIP(hipMalloc((void**)&ctx->cube, off));
-			FX_HIP(hipMemsetAsync(ctx->cube, 0, off, ctx->stream));
+			if (zeroed(&ctx->cube, off)) return rc;
 			if (d->viewport_w && d->viewport_h) {                            // the scene depth's cube (Fluid.cpp:234-236): far plane everywhere
-				FX_HIP(hipMalloc((void**)&ctx->cube_depth, off));
+				if (plain(&ctx->cube_depth, off)) return rc;
 				FX_HIP(hipMemsetD32Async((hipDeviceptr_t)ctx->cube_depth, 0x3f800000, off / 4, ctx->stream));
 			}
 			// rays cross slabs: only whole grids render.  The accelerated marches address their volumes by 32-bit byte offsets (16-byte texels:
@@ -258,18 +223,15 @@ int fx_create(fx_ctx** out, const fx_desc* d)
 				RenderAccel& A = ctx->accel;
 				render_accel_layout(ctx->g, &A);
 				const size_t ncell = (size_t)A.CX * A.CY * A.CZ, vox = ctx->g.cells_owned(), bw = render_accel_bits_words(A);
-				FX_HIP(hipMalloc((void**)&A.occ, 2 * ncell * sizeof(float)));     // the grid + the per-block maxima it is dilated from
-				FX_HIP(hipMalloc((void**)&A.alpha, vox * sizeof(float)));
-				FX_HIP(hipMalloc((void**)&A.bits, bw * sizeof(uint32_t)));
-				FX_HIP(hipMemsetAsync(A.bits, 0, bw * sizeof(uint32_t), ctx->stream));
-				FX_HIP(hipMalloc((void**)&A.list, vox * sizeof(uint32_t)));
-				FX_HIP(hipMalloc((void**)&A.cells, ncell * sizeof(uint32_t)));
-				FX_HIP(hipMalloc((void**)&A.ctr, render_accel_ctr_words(ctx->g) * sizeof(uint32_t)));
-				FX_HIP(hipMemsetAsync(A.ctr, 0, render_accel_ctr_words(ctx->g) * sizeof(uint32_t), ctx->stream));
+				if (plain(&A.occ, 2 * ncell * sizeof(float))) return rc;     // the grid + the per-block maxima it is dilated from
+				if (plain(&A.alpha, vox * sizeof(float))) return rc;
+				if (zeroed(&A.bits, bw * sizeof(uint32_t))) return rc;
+				if (plain(&A.list, vox * sizeof(uint32_t))) return rc;
+				if (plain(&A.cells, ncell * sizeof(uint32_t))) return rc;
+				if (zeroed(&A.ctr, render_accel_ctr_words(ctx->g) * sizeof(uint32_t))) return rc;
 				ctx->accel_ok = true;
 			}
-			FX_HIP(hipMalloc((void**)&ctx->sh_dev, 27 * sizeof(float)));
-			FX_HIP(hipMemsetAsync(ctx->sh_dev, 0, 27 * sizeof(float), ctx->stream));
+			if (zeroed(&ctx->sh_dev, 27 * sizeof(float))) return rc;
 		}
 		FX_HIP(hipStreamSynchronize(ctx->stream));
 		return FX_OK;
@@ -642,7 +604,7 @@ int fx_set_option(fx_ctx* ctx, uint32_t option, uint32_t value)
 		if (value > 1) return FX_E_INVALID;
 		DeviceGuard dgc(ctx->device);
 		if (value && !ctx->sample_counters) {
-			FX_HIP(hipMalloc((void**)&ctx->sample_counters, kSampleShards * 3 * sizeof(unsigned long long)));
+			if (const int rc = dev_alloc(ctx, &ctx->sample_counters, kSampleShards * 3 * sizeof(unsigned long long))) return rc;
 			FX_HIP(hipMemset(ctx->sample_counters, 0, kSampleShards * 3 * sizeof(unsigned long long)));
 		}
 		ctx->opt_count_samples = (int)value;

@@ -1,6 +1,7 @@
-// fx_host.h -- what the three host-side units of the C ABI share (fx_context.cpp: contexts, fields, timing, options;
-// fx_schedule.cpp: the simulation step over a group of slab contexts; fx_api.cpp: frame constants, rendering, stage calls, slab
-// groups): status macro, device guard, timing marks, plane ranges.  Product code: nothing from oracle/.
+// fx_host.h -- what the four host-side units of the C ABI share (fx_context.cpp: contexts, fields, timing, options;
+// fx_schedule.cpp: the simulation step over a group of slab contexts; fx_api.cpp: frame constants, rendering, light probe, slab
+// groups; fx_stage_api.cpp: the optional stages' setters, getters and stage calls): status macro, device guard, the owners of
+// device memory, timing marks, plane ranges.  Product code: nothing from oracle/.
 #pragma once
 #include "fx_context.h"
 #include <algorithm>
@@ -43,7 +44,74 @@ struct DeviceGuard {
 	~DeviceGuard() { if (changed && prev >= 0) (void)hipSetDevice(prev); }     // (nothing to restore on the usual one-device path: a guard per launch costs one hipGetDevice)
 };
 
-// ---- timing ---------------------------------------------------------------------------------
+// ---- device memory ----------------------------------------------------------------------------
+// Every allocation and free of the host units outside free_all goes through these.  One failure mapping, FX_HIP's: last_error is
+// written, HIP's sticky error cleared, hipErrorOutOfMemory gives FX_E_NOMEM and anything else FX_E_DEVICE; the pointer is null behind
+// a failure.  The try_ forms are for what a context can do without (fx_create's best-effort scratch): they report to nobody.
+namespace {   // (each unit gets its own copies, and the library exports no symbol for them)
+template <class T> hipError_t try_dev_alloc(T** p, size_t bytes)
+{
+	void* q = nullptr;
+	const hipError_t e = hipMalloc(&q, bytes);
+	if (e != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
+	*p = static_cast<T*>(q);
+	return e;
+}
+template <class T> hipError_t try_host_alloc(T** p, size_t bytes, unsigned flags)       // pinned host memory (free_all: hipHostFree)
+{
+	void* q = nullptr;
+	const hipError_t e = hipHostMalloc(&q, bytes, flags);
+	if (e != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
+	*p = static_cast<T*>(q);
+	return e;
+}
+template <class T> int dev_alloc(fx_ctx* ctx, T** p, size_t bytes) { FX_HIP(try_dev_alloc(p, bytes)); return FX_OK; }
+template <class T> int dev_keep(fx_ctx* ctx, T** p, size_t bytes) { return *p ? FX_OK : dev_alloc(ctx, p, bytes); }   // allocated by the first call that needs it, and kept
+// frees if set, nulls always, and reports a failed hipFree afterwards (hipFree waits for the device: nothing uses the memory any more)
+template <class T> int dev_free(fx_ctx* ctx, T** p)
+{
+	T* q = *p;
+	*p = nullptr;
+	if (q) FX_HIP(hipFree((void*)q));
+	return FX_OK;
+}
+// dev_alloc with the buffer zeroed on `s` (default: the context's stream); null behind a failed fill too
+template <class T> int dev_alloc_zeroed(fx_ctx* ctx, T** p, size_t bytes, hipStream_t s = nullptr)
+{
+	if (const int rc = dev_alloc(ctx, p, bytes)) return rc;
+	const hipError_t e = hipMemsetAsync(*p, 0, bytes, s ? s : ctx->stream);
+	if (e != hipSuccess) (void)dev_free(ctx, p);
+	FX_HIP(e);
+	return FX_OK;
+}
+// a kept buffer that grows: a request beyond the *have bytes of *p frees it and allocates anew (the contents go); *have stays true on every path
+template <class T> int dev_grow(fx_ctx* ctx, T** p, size_t* have, size_t bytes)
+{
+	if (*have >= bytes) return FX_OK;
+	*have = 0;
+	if (const int rc = dev_free(ctx, p)) return rc;
+	if (const int rc = dev_alloc(ctx, p, bytes)) return rc;
+	*have = bytes;
+	return FX_OK;
+}
+
+// One device allocation owned by a scope: a setter builds the new buffers beside the ones in force in owners on its stack, every early
+// return frees them, and its last lines -- which cannot fail -- swap them into the context, so that the owner then frees the old ones.
+class DevBuf {
+	void* p_ = nullptr;
+public:
+	DevBuf() = default;
+	DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+	DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+	~DevBuf() { if (p_ && hipFree(p_) != hipSuccess) (void)hipGetLastError(); }
+	int alloc(fx_ctx* ctx, size_t bytes) { if (const int rc = dev_free(ctx, &p_)) return rc; return dev_alloc(ctx, &p_, bytes); }
+	template <class T = void> T* get() const { return static_cast<T*>(p_); }
+	template <class T = void> T* release() { void* q = p_; p_ = nullptr; return static_cast<T*>(q); }
+	template <class T> void swap(T** slot) { void* q = (void*)*slot; *slot = static_cast<T*>(p_); p_ = q; }   // the commit: *slot's old buffer is this owner's now
+	int free(fx_ctx* ctx) { return dev_free(ctx, &p_); }                  // now, reporting a failure, where the destructor cannot
+};
+}  // namespace
+
 // ---- timing ---------------------------------------------------------------------------------
 enum MarkKind { MK_ADVECT, MK_DIV, MK_JACOBI, MK_PROJECT, MK_LIGHT, MK_VIEW, MK_EXCH, MK_RESOLVE, MK_JACOBI_TAIL, MK_CHAIN };
 

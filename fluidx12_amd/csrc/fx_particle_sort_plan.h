@@ -1,5 +1,5 @@
 // fx_particle_sort_plan.h -- the shape of one particle sort (fx_particle_sort.hip), decided on the host by fx_particle_sort_plan.cpp: key width,
-// digits, launches and the layout of the scratch block.  Plain C++, no HIP: the kernels, the entry points (fx_api.cpp) and the stand-alone
+// digits, launches and the layout of the scratch block.  Plain C++, no HIP: the kernels, the entry points (fx_stage_api.cpp) and the stand-alone
 // planner test (tests/test_particle_sort_ref.py) all include it.
 #pragma once
 #include <stddef.h>

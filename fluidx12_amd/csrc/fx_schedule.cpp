@@ -1,6 +1,6 @@
 // fx_schedule.cpp -- Fluid::Simulate (/root/reference/FluidX12/Content/Fluid.cpp:348-410) as a schedule of kernel launches and halo
 // exchanges over a group of z-slab contexts: one code path serves the single-GPU case, the RCCL slabs and the in-process loop-back
-// slabs.  The C ABI entry points that drive it are in fx_api.cpp; contexts, fields and options in fx_context.cpp.
+// slabs.  The C ABI entry points that drive it are in fx_api.cpp and fx_stage_api.cpp; contexts, fields and options in fx_context.cpp.
 #include "fx_host.h"
 #include <memory>
 
