@@ -39,6 +39,8 @@ MG_MAX_LEVELS = 12                                 # FX_MG_MAX_LEVELS
 MAX_PARTICLES = 1 << 26                            # FX_MAX_PARTICLES
 PARTICLES_DEVICE = 0x1                             # FX_PARTICLES_DEVICE: fx_set_particles / fx_sample_velocity take device pointers
 PARTICLE_EULER, PARTICLE_MIDPOINT = 0, 1           # FX_PARTICLE_*: fx_particle_params.scheme
+MAX_PARTICLE_SPAWNERS = 16                         # FX_MAX_PARTICLE_SPAWNERS
+SPAWN_BOX, SPAWN_BALL = 0, 1                       # FX_SPAWN_*: fx_particle_spawner.shape
 
 
 class Desc(C.Structure):
@@ -107,6 +109,16 @@ class ParticleSortInfo(C.Structure):
 
 class ParticleTrail(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("rate", C.c_float), ("tint", C.c_float * 4), ("heat", C.c_float)]
+
+
+class ParticleSpawner(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("shape", C.c_uint32), ("seed", C.c_uint32), ("center", C.c_float * 3),
+                ("half_extent", C.c_float * 3), ("rate", C.c_float), ("age_spread", C.c_float)]
+
+
+class ParticleSpawnInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("born", C.c_uint64), ("dropped", C.c_uint64), ("blocked", C.c_uint64),
+                ("serial", C.c_uint64 * 16)]
 
 
 class Timing(C.Structure):
@@ -179,6 +191,10 @@ SYMBOLS = {
     "fx_get_particle_trail": (C.c_int, [_vp, C.POINTER(ParticleTrail)]),
     "fx_deposit_particles": (C.c_int, [_vp, _vp]),
     "fx_particle_density": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.c_size_t]),
+    "fx_set_particle_spawners": (C.c_int, [_vp, C.POINTER(ParticleSpawner), C.c_uint32]),
+    "fx_get_particle_spawners": (C.c_int, [_vp, C.POINTER(ParticleSpawner), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fx_spawn_particles": (C.c_int, [_vp, _vp]),
+    "fx_particle_spawn_info": (C.c_int, [_vp, _vp, C.POINTER(ParticleSpawnInfo)]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),

@@ -256,6 +256,29 @@ public:
 		return m_status == FX_OK;
 	}
 
+	// not in the reference: the particle spawners -- records born on the device into dead slots of the set (fx_set_particle_spawners: up to
+	// FX_MAX_PARTICLE_SPAWNERS boxes and ellipsoids with a rate; nullptr or count 0 = off, the default), the stage alone (fx_spawn_particles),
+	// its counters and serials (fx_particle_spawn_info) and a set of `count` dead records to spawn into (SetParticlePool)
+	bool SetParticleSpawners(const fx_particle_spawner* list, uint32_t count) { m_status = fx_set_particle_spawners(m_ctx, list, count); return m_status == FX_OK; }
+	bool GetParticleSpawners(fx_particle_spawner* out, uint32_t capacity, uint32_t& count)
+	{
+		m_status = fx_get_particle_spawners(m_ctx, out, capacity, &count);
+		return m_status == FX_OK;
+	}
+	bool SpawnParticles(void* stream = nullptr) { m_status = fx_spawn_particles(m_ctx, stream); return m_status == FX_OK; }
+	bool ParticleSpawnInfo(struct fx_particle_spawn_info& out, void* stream = nullptr)
+	{
+		m_status = fx_particle_spawn_info(m_ctx, stream, &out);
+		return m_status == FX_OK;
+	}
+	bool SetParticlePool(uint32_t count, void* stream = nullptr)
+	{
+		std::vector<float> dead((size_t)count * 4, 0.0f);
+		for (uint32_t i = 0; i < count; ++i) dead[(size_t)i * 4 + 3] = -1.0f;
+		m_status = fx_set_particles(m_ctx, stream, count ? dead.data() : nullptr, count, 0u);
+		return m_status == FX_OK;
+	}
+
 	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
 	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }

@@ -117,6 +117,11 @@ struct fx_ctx {
 	// freed by fx_set_particle_trail alone
 	fx_particle_trail trail = { (uint32_t)sizeof(fx_particle_trail), 0u, 0.0f, { 0.0f, 0.0f, 0.0f, 0.0f }, 0.0f };
 	unsigned long long* trail_acc = nullptr;   // device; null = no trail: every call is the one it is without the feature
+	// the particle spawners (fx_set_particle_spawners; fx_particle_spawn.hip): while set, one device block laid out by `spawn` (the state and the
+	// sites, a count of dead records per workgroup, the scan's block sums), allocated and freed by fx_set_particle_spawners and fx_set_particles alone
+	std::vector<fx_particle_spawner> spawners;   // the list in force; empty = none (default)
+	void* spawn_mem = nullptr;      // device; null = no spawners: every call is the one it is without the feature
+	fx::SpawnPlan spawn = {};       // of part_count, while spawn_mem is set
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -180,6 +180,7 @@ int particles_phase(fx_ctx* ctx, hipStream_t s);     // the tracer particles one
 int sort_particles_phase(fx_ctx* ctx, hipStream_t s);   // the particle sort alone (fx_sort_particles); nothing with no set; counts into psort_sorts
 int trail_phase(fx_ctx* ctx, hipStream_t s);         // the particle trail (fx_deposit_particles): scatter and apply; nothing with no trail, no set or dt <= 0
 int trail_splat_phase(fx_ctx* ctx, hipStream_t s);   // the scatter alone (fx_particle_density); FX_E_STATE with no trail, nothing with no set
+int spawn_phase(fx_ctx* ctx, hipStream_t s);         // the particle spawners alone (fx_spawn_particles); FX_E_STATE with no spawners, nothing with no set or dt <= 0
 int simulate_impl(fx_ctx* ctx, hipStream_t s);
 
 }  // namespace fxh

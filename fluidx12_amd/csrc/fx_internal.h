@@ -216,6 +216,28 @@ hipError_t launch_particle_sort(const Geom& g, const PsortPlan& p, float* record
 hipError_t launch_trail_splat(const Geom& g, const float* records, uint32_t count, unsigned long long* acc, hipStream_t s);
 hipError_t launch_trail_apply(const Geom& g, int half_store, const fx_particle_trail& t, float dt, unsigned long long* acc, void* col, float* temp,
 	float* alpha, const uint8_t* code, hipStream_t s);
+// ---- the particle spawners (fx_particle_spawn.hip; fx_set_particle_spawners, fx_spawn_particles).  One device block: SpawnState at its head,
+// then one count of dead records per workgroup of kSpawnRecords records and the scan's block sums, laid out by spawn_plan(count).  The setter
+// fills `site` and zeroes the rest; born .. serial are what fx_particle_spawn_info copies out in one piece
+const uint32_t kSpawnThreads = 256;                           // threads of a count / place workgroup
+const uint32_t kSpawnItems = 4;                               // records each of them takes
+const uint32_t kSpawnRecords = kSpawnThreads * kSpawnItems;   // records per workgroup
+const uint32_t kSpawnScanTile = 2048;                         // workgroup counts one scan workgroup takes (256 threads x 8)
+struct SpawnSite { uint32_t shape, seed; float center[3], half[3], rate, age_spread; };
+struct SpawnState {
+	unsigned long long born, dropped, blocked, serial[FX_MAX_PARTICLE_SPAWNERS];      // the counters and the births each spawner has attempted
+	unsigned long long acc[FX_MAX_PARTICLE_SPAWNERS];                                 // the fractions, units of 2^-16 births
+	unsigned long long base[FX_MAX_PARTICLE_SPAWNERS];                                // of the run in flight: the serial of each spawner's first birth,
+	uint32_t first[FX_MAX_PARTICLE_SPAWNERS + 1];                                     // ... its first birth's number j (the last entry: n),
+	uint32_t dead, take, pad;                                                         // ... D and min(n, D)
+	SpawnSite site[FX_MAX_PARTICLE_SPAWNERS];
+};
+struct SpawnPlan { uint32_t count, wgs, scan_blocks; size_t off_counts, off_sums, bytes; };
+SpawnPlan spawn_plan(uint32_t count);                         // count 0 plans the state alone
+// records: count x (x, y, z, age) as the move has them, code: the obstacle bytes or null, mem: p.bytes of device memory holding `spawners`
+// sites.  Four launches (six when the counts need more than one scan tile); enqueues only; writes dead records and the block, nothing else.
+// count 0 is the caller's to skip
+hipError_t launch_spawn_particles(const Geom& g, const SpawnPlan& p, uint32_t spawners, float dt, float* records, const uint8_t* code, void* mem, hipStream_t s);
 // ---- which kernel of a stage's family serves a geometry and a storage type (fx_sim.hip: the one place that decides; host code, no device needed):
 // cells per thread along the row -- the scalar kernel (any extent, 2-D), 16-byte vectors, or the 4-byte-aligned pairs / triples of the vW kernels
 enum SimStage { SIM_DIVERGENCE = 0, SIM_PROJECT = 1 };

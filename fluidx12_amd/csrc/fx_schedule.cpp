@@ -827,7 +827,7 @@ int project_phase(fx_ctx* ctx, hipStream_t s)
 }
 
 // Tracer particles (fx_particles.hip): behind the projection, every live record takes one step through velocity[0], the field the projection has
-// just written.  One launch over the records, in place; it reads the velocity, the obstacle code and the open-wall bits and writes the particle
+// just written; while spawners are set (fx_particle_spawn.hip) the births follow.  The move is one launch over the records, in place; it reads the velocity, the obstacle code and the open-wall bits and writes the particle
 // buffer alone, so no field of the step knows of it.  Nothing is allocated, copied or waited for here (fx_set_particles did all of that).  Booked
 // with the projection: fx_timing has no mark of its own for it.
 int particles_phase(fx_ctx* ctx, hipStream_t s)
@@ -846,6 +846,22 @@ int particles_phase(fx_ctx* ctx, hipStream_t s)
 		}
 	}
 	FX_HIP(launch_move_particles(ctx->g, ctx->half, ctx->part_prm, ctx->vel[0], ctx->obst_code, ctx->open_faces, ctx->time_step, ctx->part, ctx->part_count, s));
+	// the births behind the move: a record born now sits on its spawn point when the step ends and moves from the next step on
+	if (ctx->spawn_mem) FX_HIP(launch_spawn_particles(ctx->g, ctx->spawn, (uint32_t)ctx->spawners.size(), ctx->time_step, ctx->part, ctx->obst_code, ctx->spawn_mem, s));
+	return FX_OK;
+}
+
+// The particle spawners alone (fx_particle_spawn.hip): the dead counted per workgroup and scanned, the rates ticked, the births placed into
+// dead slots in index order.  dt is the kernel argument taken here, at enqueue, like every other stage's; how many records a run bears is
+// decided on the device, so a captured run replayed keeps the rate.  Enqueues only (fx_set_particle_spawners and fx_set_particles did the
+// allocating); booked with the projection like the move.
+int spawn_phase(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->spawn_mem) return FX_E_STATE;
+	if (!ctx->part || !(ctx->time_step > 0.0f)) return FX_OK;
+	DeviceGuard dg(ctx->device);
+	ScopedMark mk(ctx, s, MK_PROJECT);
+	FX_HIP(launch_spawn_particles(ctx->g, ctx->spawn, (uint32_t)ctx->spawners.size(), ctx->time_step, ctx->part, ctx->obst_code, ctx->spawn_mem, s));
 	return FX_OK;
 }
 

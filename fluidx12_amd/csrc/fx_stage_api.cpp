@@ -1,5 +1,5 @@
 // fx_stage_api.cpp -- the entry points of the step's optional stages (include/fluidx_hip.h): vorticity confinement, emitters, obstacles with
-// their bodies and meshes, open walls, buoyancy, tracer particles with their sort and trail, the advection scheme and the pressure solver --
+// their bodies and meshes, open walls, buoyancy, tracer particles with their sort, trail and spawners, the advection scheme and the pressure solver --
 // each stage's setter, getter and its phase of the step (fx_schedule.cpp) on its own.  A setter that owns device memory builds the new
 // buffers beside the ones in force (DevBuf, fx_host.h) and commits in its last lines.  The per-frame calls: fx_api.cpp.
 #include "fx_host.h"
@@ -342,6 +342,14 @@ int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t c
 	fx::PsortPlan sort_plan = {};
 	const bool sorting = ctx->psort_mem != nullptr;
 	if (const int rc = sorting ? psort_alloc(ctx, count, &sort_plan, &sort_mem) : FX_OK) return rc;
+	DevBuf spawn_mem;                                                       // while spawners are set: their block for the new count, the state carried over
+	const fx::SpawnPlan spawn_plan = fx::spawn_plan(count);
+	if (ctx->spawn_mem) {
+		if (const int rc = spawn_mem.alloc(ctx, spawn_plan.bytes)) return rc;
+		FX_HIP(hipDeviceSynchronize());                                     // (no run of the stage is in flight any more: the state is final)
+		FX_HIP(hipMemcpy(spawn_mem.get(), ctx->spawn_mem, sizeof(fx::SpawnState), hipMemcpyDeviceToDevice));
+		FX_HIP(hipDeviceSynchronize());
+	}
 	if (count) {
 		const size_t bytes = (size_t)count * 16;
 		if (const int rc = fresh.alloc(ctx, bytes)) return rc;
@@ -357,6 +365,10 @@ int fx_set_particles(fx_ctx* ctx, void* stream, const float* records, uint32_t c
 		ctx->psort = sort_plan;
 	}
 	ctx->psort_runs = ctx->psort_sorts = 0;
+	if (spawn_mem.get()) {
+		spawn_mem.swap(&ctx->spawn_mem);
+		ctx->spawn = spawn_plan;
+	}
 	return fresh.free(ctx);
 }
 
@@ -503,6 +515,66 @@ int fx_particle_density(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes)
 	FX_HIP(hipMemcpyAsync(out, ctx->trail_acc, bytes, hipMemcpyDeviceToHost, s));
 	FX_HIP(hipMemsetAsync(ctx->trail_acc, 0, bytes, s));
 	FX_HIP(hipStreamSynchronize(s));
+	return FX_OK;
+}
+
+// ---- the particle spawners (fx_particle_spawn.hip) --------------------------------------------------------------
+// A list allocates the device block of the set in force (fx_set_particles resizes it from then on) and fills it: the sites, and zeroes for the
+// fractions, the serials and the counters; an empty list frees it.  The new block is built beside the one in force.  Blocks.
+int fx_set_particle_spawners(fx_ctx* ctx, const fx_particle_spawner* list, uint32_t count)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (count > FX_MAX_PARTICLE_SPAWNERS || (count && !list)) return FX_E_INVALID;
+	if (!list) count = 0;
+	for (uint32_t k = 0; k < count; ++k) {
+		const fx_particle_spawner& p = list[k];
+		if (p.struct_size != sizeof(fx_particle_spawner) || p.flags != 0) return FX_E_INVALID;
+		if (p.shape != FX_SPAWN_BOX && p.shape != FX_SPAWN_BALL) return FX_E_INVALID;
+		for (int a = 0; a < 3; ++a) if (!std::isfinite(p.center[a]) || !std::isfinite(p.half_extent[a]) || p.half_extent[a] < 0.0f) return FX_E_INVALID;
+		if (!std::isfinite(p.rate) || p.rate < 0.0f || !std::isfinite(p.age_spread) || p.age_spread < 0.0f) return FX_E_INVALID;
+	}
+	DeviceGuard dg(ctx->device);
+	DevBuf mem;
+	const fx::SpawnPlan plan = fx::spawn_plan(ctx->part_count);
+	if (count) {
+		fx::SpawnState st = {};
+		for (uint32_t k = 0; k < count; ++k) {
+			const fx_particle_spawner& p = list[k];
+			st.site[k] = fx::SpawnSite{ p.shape, p.seed, { p.center[0], p.center[1], p.center[2] }, { p.half_extent[0], p.half_extent[1], p.half_extent[2] }, p.rate, p.age_spread };
+		}
+		if (const int rc = mem.alloc(ctx, plan.bytes)) return rc;
+		FX_HIP(hipMemcpy(mem.get(), &st, sizeof st, hipMemcpyHostToDevice));
+		FX_HIP(hipDeviceSynchronize());
+	}
+	// the commit: the owner takes the old block and frees it (hipFree waits for the device: no run of the stage is in flight any more)
+	mem.swap(&ctx->spawn_mem);
+	ctx->spawn = count ? plan : fx::SpawnPlan{};
+	ctx->spawners.assign(list, list + count);
+	return mem.free(ctx);
+}
+
+int fx_get_particle_spawners(fx_ctx* ctx, fx_particle_spawner* out, uint32_t capacity, uint32_t* count)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;             // (slab ranks may ask: the list is empty there)
+	return get_list(ctx->spawners, out, capacity, count);
+}
+
+int fx_spawn_particles(fx_ctx* ctx, void* stream) { return run_stage(ctx, stream, spawn_phase); }
+
+int fx_particle_spawn_info(fx_ctx* ctx, void* stream, struct fx_particle_spawn_info* out)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!out) return FX_E_INVALID;
+	struct fx_particle_spawn_info r = {};
+	r.struct_size = (uint32_t)sizeof r;
+	if (ctx->spawn_mem) {                                                   // born, dropped, blocked, serial[]: the head of the block, in this order
+		static_assert(sizeof r - offsetof(struct fx_particle_spawn_info, born) == offsetof(fx::SpawnState, acc), "the info struct mirrors the state's head");
+		DeviceGuard dg(ctx->device);
+		hipStream_t s = pick_stream(ctx, stream);
+		FX_HIP(hipMemcpyAsync(&r.born, ctx->spawn_mem, offsetof(fx::SpawnState, acc), hipMemcpyDeviceToHost, s));
+		FX_HIP(hipStreamSynchronize(s));
+	}
+	*out = r;
 	return FX_OK;
 }
 

@@ -701,6 +701,55 @@ class Fluid:
         capi.check(self._lib.fx_particle_density(self._ctx, stream, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "ParticleDensity")
         return out
 
+    def SetParticleSpawners(self, spawners):
+        """particles born on the device (fx_set_particle_spawners): a list of up to 16 dicts with the keys "shape" ("box", "ball" or a
+        capi.SPAWN_* value; a ball is the ellipsoid with the half extents as semi-axes), "seed", "center" and "half_extent" (texture space),
+        "rate" (births per second), "age_spread" (a new record's age is u * age_spread) and optionally "flags".  While set, the particle stage
+        of Simulate and MoveParticles bears records into dead slots of the set behind the move.  Replaces the list and zeroes the serials and
+        counters; None or an empty list switches it off (the default).  Configuration: kept across UpdateFrame, not stored in checkpoints.
+        Whole-grid contexts only."""
+        self._need()
+        spawners = list(spawners or [])
+        arr = (capi.ParticleSpawner * max(len(spawners), 1))()
+        for e, d in zip(arr, spawners):
+            e.struct_size, e.flags = C.sizeof(capi.ParticleSpawner), int(d.get("flags", 0))
+            shape = d.get("shape", "box")
+            e.shape = {"box": capi.SPAWN_BOX, "ball": capi.SPAWN_BALL}.get(shape, shape)
+            e.seed = int(d.get("seed", 0)) & 0xFFFFFFFF
+            e.center = (C.c_float * 3)(*[float(v) for v in d["center"]])
+            e.half_extent = (C.c_float * 3)(*[float(v) for v in d["half_extent"]])
+            e.rate, e.age_spread = float(d["rate"]), float(d.get("age_spread", 0.0))
+        capi.check(self._lib.fx_set_particle_spawners(self._ctx, arr if spawners else None, len(spawners)), "SetParticleSpawners")
+
+    def GetParticleSpawners(self):
+        """the list in force (fx_get_particle_spawners), as dicts with the keys SetParticleSpawners takes"""
+        self._need()
+        n = C.c_uint32(0)
+        arr = (capi.ParticleSpawner * capi.MAX_PARTICLE_SPAWNERS)()
+        capi.check(self._lib.fx_get_particle_spawners(self._ctx, arr, capi.MAX_PARTICLE_SPAWNERS, C.byref(n)), "GetParticleSpawners")
+        return [{"shape": {capi.SPAWN_BOX: "box", capi.SPAWN_BALL: "ball"}.get(e.shape, e.shape), "seed": e.seed, "center": tuple(e.center),
+                 "half_extent": tuple(e.half_extent), "rate": e.rate, "age_spread": e.age_spread, "flags": e.flags} for e in arr[:n.value]]
+
+    def SpawnParticles(self, stream=None):
+        """the spawn stage alone (fx_spawn_particles): one step's births into the dead slots of the set; enqueues only"""
+        self._need()
+        capi.check(self._lib.fx_spawn_particles(self._ctx, stream), "SpawnParticles")
+
+    def ParticleSpawnInfo(self, stream=None):
+        """the counters since the last SetParticleSpawners (fx_particle_spawn_info; waits for the stream) as a dict: "born" (records stored),
+        "dropped" (births that found no dead slot), "blocked" (births inside a solid) and "serial" (per spawner, the births attempted)"""
+        self._need()
+        r = capi.ParticleSpawnInfo()
+        r.struct_size = C.sizeof(capi.ParticleSpawnInfo)
+        capi.check(self._lib.fx_particle_spawn_info(self._ctx, stream, C.byref(r)), "ParticleSpawnInfo")
+        return {"born": int(r.born), "dropped": int(r.dropped), "blocked": int(r.blocked), "serial": [int(v) for v in r.serial]}
+
+    def SetParticlePool(self, n, stream=None):
+        """a set of `n` dead records (0, 0, 0, -1) (SetParticles): how a set that is only ever spawned into starts"""
+        rec = np.zeros((int(n), 4), np.float32)
+        rec[:, 3] = -1.0
+        self.SetParticles(rec, stream)
+
     def SampleVelocity(self, points, stream=None, out=None):
         """the velocity at points of texture space (fx_sample_velocity): `points` (n, 3) or (n, 4) (a fourth column is ignored) as anything numpy
         takes -> float32 (n, 3), blocking; or a float32 torch tensor (n, 4) on the context's device with `out` a float32 tensor (n, 3) there:

@@ -175,7 +175,8 @@ int fx_update_frame(fx_ctx* ctx, float time_step, uint8_t frame_index,
  *   divergence               VELOCITY1                                                                      -> DIVERGENCE
  *   solve                    DIVERGENCE, PRESSURE as the previous step (or an upload) left it               -> PRESSURE
  *   project                  VELOCITY1, PRESSURE                                                            -> VELOCITY
- *   particles                the sort when this run of the stage is due one, then the move through the VELOCITY just projected
+ *   particles                the sort when this run of the stage is due one, then the move through the VELOCITY just projected, then the
+ *                            births while spawners are set (fx_set_particle_spawners)
  * Behind the step FX_FIELD_VELOCITY1 holds what the divergence read, FX_FIELD_COLOR_PREV what the advection sampled. */
 int fx_simulate(fx_ctx* ctx, void* stream, uint8_t frame_index);
 /* Fluid::Render (Fluid.cpp:412-446), all four flag combinations:
@@ -630,8 +631,8 @@ int fx_heat(fx_ctx* ctx, void* stream);
  * call but the three getters) a context that owns fewer planes than the grid -- slab ranks of every transport, on the confinement's footing;
  * the getters succeed there and report the empty default, as fx_get_emitters does.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts.  FX_E_NOMEM:
  * the buffer cannot be allocated.
- * Out of scope: spawning on the device; drawing
- * particles in the library's renders; momentum deposit, i.e. drag back on the flow (smoke and heat the particles do leave behind:
+ * Out of scope: drawing
+ * particles in the library's renders (births on the device: fx_set_particle_spawners below); momentum deposit, i.e. drag back on the flow (smoke and heat the particles do leave behind:
  * fx_set_particle_trail below); sampling colour or temperature at points. */
 #define FX_MAX_PARTICLES      (1u << 26)
 #define FX_PARTICLES_DEVICE   0x1u      /* the pointer(s) are device memory of the context's device */
@@ -688,7 +689,7 @@ int fx_sample_velocity(fx_ctx* ctx, void* stream, const float* points, uint32_t 
  * report the default there) slab ranks.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts; fx_sort_particles and fx_particle_order_device while
  * sorting is not enabled.  FX_E_NOMEM: the scratch cannot be allocated.
  * (struct fx_particle_sort_info has no typedef: C keeps a typedef and the function of that name in one name space.)
- * Out of scope: spawning on the device; other orders (Morton, tiles); sorting by anything but cell; slab contexts. */
+ * Out of scope: other orders (Morton, tiles) (births on the device: fx_set_particle_spawners below); sorting by anything but cell; slab contexts. */
 typedef struct fx_particle_sort {
 	uint32_t struct_size, flags;   /* sizeof(fx_particle_sort) = 16; flags: 0 */
 	uint32_t enabled;              /* 0 (default): no scratch, no sort anywhere; 1: scratch allocated for the current and every later set */
@@ -738,7 +739,7 @@ int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32);
  * rate < 0, bytes != X * Y * Z * 8, and (all but fx_get_particle_trail, which reports the default there) slab ranks.  FX_E_STATE:
  * FX_FLAG_RENDER_ONLY contexts; fx_deposit_particles and fx_particle_density while no trail is set.  FX_E_NOMEM: the accumulator cannot be
  * allocated.
- * Out of scope: per-particle strength or fading by age (the record has no room for it); momentum deposit; spawning; drawing; slab contexts;
+ * Out of scope: per-particle strength or fading by age (the record has no room for it); momentum deposit; drawing; slab contexts (births: fx_set_particle_spawners below);
  * restricting the apply pass to the set's bounding box; checkpointing. */
 typedef struct fx_particle_trail {
 	uint32_t struct_size, flags;   /* sizeof(fx_particle_trail) = 32; flags: 0 */
@@ -750,6 +751,70 @@ int fx_set_particle_trail(fx_ctx* ctx, const fx_particle_trail* trail);
 int fx_get_particle_trail(fx_ctx* ctx, fx_particle_trail* out);
 int fx_deposit_particles(fx_ctx* ctx, void* stream);
 int fx_particle_density(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes);
+
+/* Particle spawners (no reference counterpart): tracer particles born on the device.  The set above ages and dies -- by lifetime, through open
+ * walls, and, once sorted, into the tail [live, count) --; while spawners are set, up to FX_MAX_PARTICLE_SPAWNERS boxes and ellipsoids bear
+ * new records at a rate, each birth taking a dead record's slot: spawn -> move -> deposit -> die -> slot reused, with no upload and no kernel
+ * of the caller's.  The count per step lives in device memory, so a replayed graph keeps spawning at the right rate.  Four launches
+ * (fx_particle_spawn.hip): a count of the dead per workgroup, its scan, the tick of the rates, the placement; no atomic decides a slot, the
+ * result is the same bit for bit on every run.  Off by default: a context that never calls the setter launches what it did before.
+ * The rule (tests/particle_spawn_ref.py restates it in numpy).  All integer arithmetic is unsigned and wraps; all floating point is fp32,
+ * every operation rounded as written; c(v) = fminf(fmaxf(v, 0), 1); dt = the time step of the last fx_update_frame, taken at enqueue.
+ *   state    in device memory, per spawner s: acc_s, a uint64 fraction in units of 2^-16 births, and serial_s, a uint64 count of the births
+ *            the spawner has attempted; and the three uint64 counters born, dropped, blocked
+ *   count    w = fminf(rate_s * dt, 67108864.0f);  inc = (uint64)llrintf(w * 65536.0f);  acc_s += inc;  n_s = acc_s >> 16;  acc_s &= 0xFFFF.
+ *            The step's births are numbered j = 0 ... n - 1, n = sum of n_s: spawner 0's first, in serial order, then spawner 1's, and so
+ *            on; first_s = the number of spawner s's first birth.  Birth j of spawner s has the serial k = serial_s + (j - first_s); behind
+ *            the step serial_s += n_s, whether or not a birth found a slot: a record is a function of (seed, s, k) and nothing else
+ *   slots    a record is dead iff !(age >= 0), the move's own test (-0.0 is live, a NaN is dead); D = the number of dead records.  Birth j
+ *            takes the j-th dead record of the buffer in index order.  Births j >= D are dropped and `dropped` grows by n - D: the last
+ *            spawners starve first.  A live record never changes by a bit.  Behind a sort the dead are the tail, so births append;
+ *            *live_u32 and order stay those of the last sort, as they do when records die between sorts
+ *   words    mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *            h0 = mix(seed + 0x9e3779b9 * (s + 1));  h1 = mix(h0 ^ (uint32)k);  h2 = mix(h1 ^ (uint32)(k >> 32))
+ *            word(d) = mix(h2 + 0x85ebca6b * (d + 1));  u(d) = (float)(word(d) >> 8) * 0x1p-24f, exact, in [0, 1);
+ *            a(d) = fmaf(2, u(d), -1), exact, in [-1, 1)
+ *   place    FX_SPAWN_BOX: (ax, ay, az) = (a(0), a(1), a(2)).  FX_SPAWN_BALL: tries t = 0 ... 7 with (a(3t), a(3t + 1), a(3t + 2)), taking
+ *            the first with fmaf(az, az, fmaf(ay, ay, ax * ax)) <= 1, and (0, 0, 0) if none passes (0.476^8, about one birth in 400).  On a
+ *            2-D grid az is 0 for either shape, before the test.  p_a = c(fmaf(a_a, half_extent_a, center_a)) + 0.0f
+ *   age      u(24) * age_spread, which is >= 0: the record is live
+ *   solids   with a mask set (fx_set_obstacles): the cell min((int)(p_a * N_a), N_a - 1) per axis, z cell 0 on a 2-D grid; if it is solid
+ *            (code bit 6, the bit the move tests) the birth is blocked: its slot is not stored and stays dead with every bit kept, and
+ *            `blocked` grows by one.  `born` counts the records stored
+ * fx_set_particle_spawners replaces the list and zeroes the state and the three counters; count 0 or NULL = off (the default), which frees
+ * the device block.  The block (one word per 1024 records, the state) is allocated here for the set in force and resized by every later
+ * fx_set_particles, which keeps fractions, serials and counters (FX_E_NOMEM there leaves the previous set and block in force).  All
+ * allocation and waiting happens in these two calls: fx_spawn_particles and the step only enqueue (a captured fx_simulate stays capturable).
+ * fx_simulate runs the stage inside the particle stage, behind the move (sort if due, move, spawn), when the time step is > 0, a set exists
+ * and spawners are set: a record born in a step sits on its spawn point with its spawn age when the step ends, is drawn there, deposits
+ * there in the next step's trail and moves from the next step on.  fx_move_particles does the same.  Timing: booked into
+ * fx_timing.project_ms, like the move.  fx_spawn_particles is the stage alone: FX_OK and nothing done -- the state does not tick -- while no
+ * set exists or dt <= 0.
+ * fx_get_particle_spawners: the list in force, as fx_get_emitters reports its own.
+ * fx_particle_spawn_info waits for `stream`: the three counters and the serials since the last fx_set_particle_spawners (all 0 while off).
+ * A set that is only ever spawned into starts as `count` records (0, 0, 0, -1).
+ * Configuration on the particles' terms: per context, kept across fx_update_frame, not checkpointed, not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx or out-pointer, a wrong struct_size, unknown flag bits, an unknown shape,
+ * count > FX_MAX_PARTICLE_SPAWNERS, a count with a NULL list, a non-finite member, a negative rate, half_extent or age_spread, and (all but
+ * fx_get_particle_spawners and fx_particle_spawn_info, which report the empty default there) slab ranks.  FX_E_STATE: FX_FLAG_RENDER_ONLY
+ * contexts; fx_spawn_particles while no spawners are set.  FX_E_NOMEM: the block cannot be allocated.
+ * (struct fx_particle_spawn_info has no typedef, as fx_particle_sort_info has none.)
+ * Out of scope: initial velocities (the record has no room for them); per-spawner lifetimes; Gaussian shapes; drawing; slab contexts. */
+#define FX_MAX_PARTICLE_SPAWNERS 16u
+#define FX_SPAWN_BOX  0u
+#define FX_SPAWN_BALL 1u     /* an ellipsoid with the half extents as semi-axes */
+typedef struct fx_particle_spawner {
+	uint32_t struct_size, flags;      /* sizeof(fx_particle_spawner) = 48; flags: 0 */
+	uint32_t shape, seed;             /* FX_SPAWN_*; any seed */
+	float center[3], half_extent[3];  /* texture space, as fx_emitter.center; finite, half_extent >= 0 */
+	float rate;                       /* births per second; finite, >= 0 */
+	float age_spread;                 /* finite, >= 0: a new record's age is u * age_spread, so that a burst does not die in one frame */
+} fx_particle_spawner;
+struct fx_particle_spawn_info { uint32_t struct_size, reserved; uint64_t born, dropped, blocked; uint64_t serial[FX_MAX_PARTICLE_SPAWNERS]; };   /* 160 bytes */
+int fx_set_particle_spawners(fx_ctx* ctx, const fx_particle_spawner* list, uint32_t count);
+int fx_get_particle_spawners(fx_ctx* ctx, fx_particle_spawner* out, uint32_t capacity, uint32_t* count);
+int fx_spawn_particles(fx_ctx* ctx, void* stream);
+int fx_particle_spawn_info(fx_ctx* ctx, void* stream, struct fx_particle_spawn_info* out);
 
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
