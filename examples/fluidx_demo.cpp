@@ -13,6 +13,8 @@
 //        [-advection maccormack|semi-lagrangian]     (the advection scheme, fx_set_advection_scheme; default: the reference's semi-Lagrangian step)
 //        [-multigrid]     (the pressure solve as two multigrid V(2,2) cycles instead of the Jacobi sweeps, fx_set_pressure_solver)
 //        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
+//        [-embers N]     (N tracer particles born at the built-in impulse, fx_set_particle_spawners, and drawn on top of the volume as glowing points that
+//                         the smoke in front of them dims, fx_set_particle_draw; 3-D grids)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
 #include "../fluidx12_amd/csrc/Fluid.hpp"
 #include <chrono>
@@ -112,6 +114,7 @@ int main(int argc, char** argv)
 	uint32_t openWalls = 0;                             // not in the reference: its box is closed on all six faces
 	uint32_t advection = FX_ADVECT_SEMI_LAGRANGIAN;     // not in the reference: its advection is semi-Lagrangian
 	bool multigrid = false;                             // not in the reference: its pressure solve is Jacobi sweeps
+	uint32_t embers = 0;                                // not in the reference: it has no particles
 	bool lightSet = false, pointLight = false, colorSet = false, ambientSet = false;   // not in the reference: its light is three constants (Fluid.cpp:169-173)
 	float lightPos[3] = { 75.0f, 75.0f, -75.0f }, lightColor[4] = {}, ambient[4] = {};
 	for (int i = 1; i < argc; ++i) {
@@ -143,6 +146,7 @@ int main(int argc, char** argv)
 			else { std::fprintf(stderr, "-advection %s: maccormack or semi-lagrangian\n", v); return 1; }
 		}
 		else if (!std::strcmp(argv[i], "-multigrid")) multigrid = true;
+		else if (!std::strcmp(argv[i], "-embers") && i + 1 < argc) embers = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
 		else if (!std::strcmp(argv[i], "-light") && i + 3 < argc) { for (float& v : lightPos) v = (float)atof(argv[++i]); lightSet = true; }
 		else if (!std::strcmp(argv[i], "-pointLight")) { pointLight = true; lightSet = true; }
 		else if (!std::strcmp(argv[i], "-lightColor") && i + 4 < argc) { for (float& v : lightColor) v = (float)atof(argv[++i]); colorSet = lightSet = true; }
@@ -233,6 +237,15 @@ int main(int argc, char** argv)
 		const fx_pressure_solver mg = Fluid::MultigridDefaults(grid.z > 1);
 		if (!fluid.SetPressureSolver(&mg)) { std::fprintf(stderr, "-multigrid: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	}
+	if (embers) {                                       // a pool of dead records, one ball spawner at the impulse that refills it over a lifetime, the draw
+		const float lifetime = 2.0f, young[4] = { 1.0f, 0.6f, 0.2f, 4.0f }, old[4] = { 0.6f, 0.1f, 0.0f, 1.0f };
+		fx_particle_params prm = { (uint32_t)sizeof(fx_particle_params), 0u, FX_PARTICLE_MIDPOINT, { 0.0f, 0.0f, 0.0f }, lifetime };
+		const fx_particle_spawner ball = { (uint32_t)sizeof(fx_particle_spawner), 0u, FX_SPAWN_BALL, 1u, { 0.5f, 0.1f, 0.5f }, { 0.05f, 0.05f, 0.05f }, embers / lifetime, 0.0f };
+		if (!fluid.SetParticlePool(embers) || !fluid.SetParticleParams(&prm) || !fluid.SetParticleSpawners(&ball, 1) || !fluid.SetParticleDraw(young, old)) {
+			std::fprintf(stderr, "-embers %u: %s\n", (unsigned)embers, fx_error_string(fluid.LastStatus()));
+			return 1;
+		}
+	}
 	if (lightSet && grid.z <= 1) std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: a 2-D grid has no light; ignored\n");
 	if (lightSet && grid.z > 1 && !fluid.SetLight(lightPos, pointLight, colorSet ? lightColor : nullptr, ambientSet ? ambient : nullptr)) {
 		std::fprintf(stderr, "-light / -pointLight / -lightColor / -ambient: %s\n", fx_error_string(fluid.LastStatus()));
@@ -263,6 +276,7 @@ int main(int argc, char** argv)
 			fluid.ClearRenderTarget(nullptr, clearColor);
 			if (radiance) probe.RenderEnvironment(fluid, nullptr, frameIndex);      // FluidX12.cpp:483: the sky first
 			fluid.Render(nullptr, frameIndex, Fluid::OPTIMIZED);                    // marches + renderCube onto the target
+			if (embers) fluid.DrawParticles(frameIndex);                            // the embers on top, dimmed by the smoke in front of them
 		}
 		if (fluid.LastStatus() != FX_OK) { std::fprintf(stderr, "frame %u: %s\n", f, fx_error_string(fluid.LastStatus())); return 1; }
 	}

@@ -41,6 +41,7 @@ PARTICLES_DEVICE = 0x1                             # FX_PARTICLES_DEVICE: fx_set
 PARTICLE_EULER, PARTICLE_MIDPOINT = 0, 1           # FX_PARTICLE_*: fx_particle_params.scheme
 MAX_PARTICLE_SPAWNERS = 16                         # FX_MAX_PARTICLE_SPAWNERS
 SPAWN_BOX, SPAWN_BALL = 0, 1                       # FX_SPAWN_*: fx_particle_spawner.shape
+DRAW_AMOUNT_ONE = 1 << 37                          # fx_particle_splats: what an unoccluded particle whose footprint is on screen adds to a pixel pair in total
 
 
 class Desc(C.Structure):
@@ -114,6 +115,10 @@ class ParticleTrail(C.Structure):
 class ParticleSpawner(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("shape", C.c_uint32), ("seed", C.c_uint32), ("center", C.c_float * 3),
                 ("half_extent", C.c_float * 3), ("rate", C.c_float), ("age_spread", C.c_float)]
+
+
+class ParticleDraw(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("color", C.c_float * 4), ("end_color", C.c_float * 4)]
 
 
 class ParticleSpawnInfo(C.Structure):
@@ -195,6 +200,10 @@ SYMBOLS = {
     "fx_get_particle_spawners": (C.c_int, [_vp, C.POINTER(ParticleSpawner), C.c_uint32, C.POINTER(C.c_uint32)]),
     "fx_spawn_particles": (C.c_int, [_vp, _vp]),
     "fx_particle_spawn_info": (C.c_int, [_vp, _vp, C.POINTER(ParticleSpawnInfo)]),
+    "fx_set_particle_draw": (C.c_int, [_vp, C.POINTER(ParticleDraw)]),
+    "fx_get_particle_draw": (C.c_int, [_vp, C.POINTER(ParticleDraw)]),
+    "fx_draw_particles": (C.c_int, [_vp, _vp, C.c_uint8]),
+    "fx_particle_splats": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.c_size_t]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),

@@ -279,6 +279,25 @@ public:
 		return m_status == FX_OK;
 	}
 
+	// not in the reference: the particle draw -- the live particles as emissive points on the render target, each dimmed by the smoke the
+	// direct view march shows in front of it (fx_set_particle_draw: colour x intensity at age 0 and at the lifetime; nullptr = off, the
+	// default), the draw itself on top of Render / RenderCube (fx_draw_particles) and the splat alone copied to the host
+	// (fx_particle_splats: uint64[H][W][2])
+	bool SetParticleDraw(const fx_particle_draw* draw) { m_status = fx_set_particle_draw(m_ctx, draw); return m_status == FX_OK; }
+	bool SetParticleDraw(const float color[4], const float endColor[4])
+	{
+		const fx_particle_draw d = { (uint32_t)sizeof(fx_particle_draw), 0u, { color[0], color[1], color[2], color[3] },
+			{ endColor[0], endColor[1], endColor[2], endColor[3] } };
+		return SetParticleDraw(&d);
+	}
+	bool GetParticleDraw(fx_particle_draw& out) { m_status = fx_get_particle_draw(m_ctx, &out); return m_status == FX_OK; }
+	bool DrawParticles(uint8_t frameIndex = 0, void* stream = nullptr) { m_status = fx_draw_particles(m_ctx, stream, frameIndex); return m_status == FX_OK; }
+	bool ParticleSplats(uint64_t* out, size_t bytes, void* stream = nullptr)
+	{
+		m_status = fx_particle_splats(m_ctx, stream, out, bytes);
+		return m_status == FX_OK;
+	}
+
 	// not in the reference (its advection is semi-Lagrangian): the advection scheme of Simulate and Advect (fx_set_advection_scheme;
 	// FX_ADVECT_SEMI_LAGRANGIAN, the default, or FX_ADVECT_MACCORMACK)
 	bool SetAdvectionScheme(uint32_t scheme) { m_status = fx_set_advection_scheme(m_ctx, scheme); return m_status == FX_OK; }

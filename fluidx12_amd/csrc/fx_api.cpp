@@ -11,6 +11,23 @@
 using namespace fx;
 using namespace fxh;
 
+// the zero fill is ordered on the stream the target is about to be used on (the context's streams do not synchronise
+// with the NULL stream)
+int fxh::ensure_target(fx_ctx* ctx, hipStream_t s)
+{
+	if (ctx->target) return FX_OK;
+	const size_t n = (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h;
+	if (!n) return FX_E_INVALID;
+	DevBuf t, tf;                                  // (both or neither: `target` alone says whether they are there)
+	if (const int rc = t.alloc(ctx, n * 4)) return rc;
+	FX_HIP(hipMemsetAsync(t.get(), 0, n * 4, s));
+	if (const int rc = tf.alloc(ctx, n * 16)) return rc;
+	FX_HIP(hipMemsetAsync(tf.get(), 0, n * 16, s));
+	ctx->target = t.release<uint8_t>();
+	ctx->target_float = tf.release<float>();
+	return FX_OK;
+}
+
 extern "C" {
 
 int fx_abi_version(void) { return FX_ABI_VERSION; }
@@ -107,23 +124,6 @@ int fx_simulate(fx_ctx* ctx, void* stream, uint8_t frame_index)
 	if (!is_driver(ctx)) return FX_OK;             // loop-back group: rank 0 drives every member
 	ctx->last_step_stream = pick_stream(ctx, stream);
 	return simulate_impl(ctx, ctx->last_step_stream);
-}
-
-// the zero fill is ordered on the stream the target is about to be used on (the context's streams do not synchronise
-// with the NULL stream)
-static int ensure_target(fx_ctx* ctx, hipStream_t s)
-{
-	if (ctx->target) return FX_OK;
-	const size_t n = (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h;
-	if (!n) return FX_E_INVALID;
-	DevBuf t, tf;                                  // (both or neither: `target` alone says whether they are there)
-	if (const int rc = t.alloc(ctx, n * 4)) return rc;
-	FX_HIP(hipMemsetAsync(t.get(), 0, n * 4, s));
-	if (const int rc = tf.alloc(ctx, n * 16)) return rc;
-	FX_HIP(hipMemsetAsync(tf.get(), 0, n * 16, s));
-	ctx->target = t.release<uint8_t>();
-	ctx->target_float = tf.release<float>();
-	return FX_OK;
 }
 
 // the scene depth's kernel argument (fx_set_scene_depth) for the cube mip `lod` (fx_render, fx_render_cube); false when none is attached

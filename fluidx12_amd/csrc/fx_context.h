@@ -122,6 +122,10 @@ struct fx_ctx {
 	std::vector<fx_particle_spawner> spawners;   // the list in force; empty = none (default)
 	void* spawn_mem = nullptr;      // device; null = no spawners: every call is the one it is without the feature
 	fx::SpawnPlan spawn = {};       // of part_count, while spawn_mem is set
+	// the particle draw (fx_set_particle_draw; fx_particle_draw.hip): while set, two uint64 per pixel of the viewport, all zero between calls;
+	// allocated and freed by fx_set_particle_draw alone
+	fx_particle_draw draw = { (uint32_t)sizeof(fx_particle_draw), 0u, { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+	unsigned long long* draw_acc = nullptr;    // device; null = no draw: every call is the one it is without the feature
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

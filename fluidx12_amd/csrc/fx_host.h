@@ -143,6 +143,7 @@ struct ScopedMark {
 
 int drain_timing(fx_ctx* c);
 int ensure_stage(fx_ctx* ctx, size_t bytes);
+int ensure_target(fx_ctx* ctx, hipStream_t s);   // fx_api.cpp: the render target and its float twin, zeroed on `s`, where no call has allocated them yet
 void free_all(fx_ctx* c);
 void destroy_lanes(fx_comm_group* g);
 void group_release(fx_comm_group* g);

@@ -216,6 +216,14 @@ hipError_t launch_particle_sort(const Geom& g, const PsortPlan& p, float* record
 hipError_t launch_trail_splat(const Geom& g, const float* records, uint32_t count, unsigned long long* acc, hipStream_t s);
 hipError_t launch_trail_apply(const Geom& g, int half_store, const fx_particle_trail& t, float dt, unsigned long long* acc, void* col, float* temp,
 	float* alpha, const uint8_t* code, hipStream_t s);
+// ---- the particle draw (fx_particle_draw.hip; fx_set_particle_draw, fx_draw_particles, fx_particle_splats).  acc: two uint64 per pixel of the
+// W x H viewport, all zero between calls.  splat: every live record that projects onto the viewport adds its amounts, dimmed by the alpha of the
+// direct view march of its pixel through `color` (wvp: the forward WorldViewProj rows, depth: the scene depth float[H][W] or null, ns: the merged
+// direct march's sample count); hipErrorInvalidValue for a 2-D grid or one beyond fx_render's limits; count 0 is the caller's to skip.
+// resolve: the pixels with a non-zero pair blend into target, every pixel stores out_float, the pairs are cleared.  Both enqueue only
+hipError_t launch_draw_splat(const Geom& g, int half_store, const void* color, const FrameConsts& fc, const float wvp[16], const float* depth, int W, int H,
+	uint32_t ns, float lifetime, const float* records, uint32_t count, unsigned long long* acc, hipStream_t s);
+hipError_t launch_draw_resolve(const fx_particle_draw& dr, int W, int H, unsigned long long* acc, uint8_t* target, float* out_float, hipStream_t s);
 // ---- the particle spawners (fx_particle_spawn.hip; fx_set_particle_spawners, fx_spawn_particles).  One device block: SpawnState at its head,
 // then one count of dead records per workgroup of kSpawnRecords records and the scan's block sums, laid out by spawn_plan(count).  The setter
 // fills `site` and zeroes the rest; born .. serial are what fx_particle_spawn_info copies out in one piece

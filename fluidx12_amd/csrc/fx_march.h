@@ -636,6 +636,51 @@ __device__ __forceinline__ void march_ray(const Geom& g, const V& vol, const uin
 	}
 }
 
+// The alpha of march_ray alone (the particle draw, fx_particle_draw.hip: the opacity in front of a scene point): the same loop with what alpha
+// does not depend on left out -- no light map, no light rays, no colour channels --, one sample per round trip like the merged march it restates.
+// Every operation sa goes through is march_ray's, in its order, so the result is that march's sa bit for bit.
+template <class V>
+__device__ __forceinline__ float march_alpha(const Geom& g, const V& vol, const float o[3], const float d[3], float tMax, uint32_t numSamples, bool go)
+{
+	const float stepScale = 3.46410155f / (float)numSamples;
+	float sa = 0.0f, t = 0.0f, prev = 0.0f;
+	uint32_t i = 0;
+	bool live = go;
+	while (live) {
+		// phase 1: samples that cannot be seen only advance the ray
+		Base b0;
+		bool gather = false;
+		while (true) {
+			if (i >= numSamples) { live = false; break; }
+			const float qx = fmaf(d[0], t, o[0]), qy = fmaf(d[1], t, o[1]), qz = fmaf(d[2], t, o[2]);
+			if (outside(qx, qy, qz)) { live = false; break; }
+			b0 = make_base(g, fmaf(qx, 0.5f, 0.5f), fmaf(qy, 0.5f, 0.5f), fmaf(qz, 0.5f, 0.5f));
+			if (vol.visible(b0)) { gather = true; break; }
+			++i;
+			t = t + stepScale;
+			if (tMax < t) { live = false; break; }
+		}
+		// phase 2: the lanes with a sample to look at gather its alpha together
+		if (gather) {
+			const float a = vol.density(make_taps(g, b0));
+			float newStep = stepScale;
+			if (0.00999999978f < a) {
+				const float transm = -sa + 1.0f;
+				newStep = step_factor(-prev + a, transm, a) * stepScale;
+				sa = fmaf(0.800000012f * a, transm, sa);
+				if (transm < 0.00999999978f) live = false;
+				prev = a;
+			}
+			if (live) {
+				++i;
+				t = t + newStep;
+				if (tMax < t) live = false;
+			}
+		}
+	}
+	return sa;
+}
+
 // cube-map texel -> ray (CSRayMarch.hlsl:107-118, GetLocalPos :39-64); false = no ray (the texel is left untouched, :116)
 __device__ __forceinline__ bool cube_texel_ray(const FrameConsts& fc, int face, int x, int y, int size, float o[3], float d[3], float& tMax)
 {

@@ -1,5 +1,5 @@
 // fx_stage_api.cpp -- the entry points of the step's optional stages (include/fluidx_hip.h): vorticity confinement, emitters, obstacles with
-// their bodies and meshes, open walls, buoyancy, tracer particles with their sort, trail and spawners, the advection scheme and the pressure solver --
+// their bodies and meshes, open walls, buoyancy, tracer particles with their sort, trail, spawners and draw, the advection scheme and the pressure solver --
 // each stage's setter, getter and its phase of the step (fx_schedule.cpp) on its own.  A setter that owns device memory builds the new
 // buffers beside the ones in force (DevBuf, fx_host.h) and commits in its last lines.  The per-frame calls: fx_api.cpp.
 #include "fx_host.h"
@@ -575,6 +575,87 @@ int fx_particle_spawn_info(fx_ctx* ctx, void* stream, struct fx_particle_spawn_i
 		FX_HIP(hipStreamSynchronize(s));
 	}
 	*out = r;
+	return FX_OK;
+}
+
+// ---- the particle draw (fx_particle_draw.hip) --------------------------------------------------------------------
+// what its calls want beside sim_guard: a 3-D grid with a viewport to project it onto
+static int draw_guard(const fx_ctx* ctx)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (ctx->g.Zg <= 1 || !ctx->desc.viewport_w || !ctx->desc.viewport_h) return FX_E_INVALID;
+	// (fx_render's limits: tap indices are 32 bits wide and put together by 24-bit multiplies, fx_march.h make_taps)
+	if ((uint64_t)ctx->g.Y * ((uint64_t)ctx->g.Zg + 1) >= (1u << 24) || ctx->g.cells_owned() >= ((size_t)1 << 32)) return FX_E_INVALID;
+	return FX_OK;
+}
+
+// The accumulator is allocated, zeroed, by the first call that sets a draw and freed by NULL; a later call replaces the colours and keeps it (it is
+// all zero between calls).  The render target too, where no render has allocated it yet.  Blocks.
+int fx_set_particle_draw(fx_ctx* ctx, const fx_particle_draw* d)
+{
+	if (const int rc = draw_guard(ctx)) return rc;
+	DeviceGuard dg(ctx->device);
+	if (!d) {
+		const int freed = dev_free(ctx, &ctx->draw_acc);                     // (waits for the device: no draw is in flight any more)
+		const fx_particle_draw off = { (uint32_t)sizeof(fx_particle_draw), 0u, { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
+		ctx->draw = off;
+		return freed;
+	}
+	if (d->struct_size != sizeof(fx_particle_draw) || d->flags != 0) return FX_E_INVALID;
+	for (int a = 0; a < 4; ++a)
+		if (!std::isfinite(d->color[a]) || d->color[a] < 0.0f || !std::isfinite(d->end_color[a]) || d->end_color[a] < 0.0f) return FX_E_INVALID;
+	DevBuf acc;
+	if (!ctx->draw_acc) {
+		const size_t bytes = (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h * 2 * sizeof(unsigned long long);
+		if (const int rc = acc.alloc(ctx, bytes)) return rc;
+		FX_HIP(hipMemsetAsync(acc.get(), 0, bytes, ctx->stream));
+	}
+	if (const int rc = ensure_target(ctx, ctx->stream)) return rc;
+	FX_HIP(hipStreamSynchronize(ctx->stream));
+	if (acc.get()) ctx->draw_acc = acc.release<unsigned long long>();
+	ctx->draw = *d;
+	return FX_OK;
+}
+
+int fx_get_particle_draw(fx_ctx* ctx, fx_particle_draw* out) { return get_setting(ctx, &fx_ctx::draw, out); }
+
+// the splat of the set in force through the colour field fx_render marches; nothing with no set
+static int draw_splat(fx_ctx* ctx, hipStream_t s)
+{
+	if (!ctx->part || !ctx->part_count) return FX_OK;
+	FX_HIP(launch_draw_splat(ctx->g, ctx->half, ctx->col[ctx->frame_parity], ctx->fc, ctx->wvp, ctx->depth, (int)ctx->desc.viewport_w,
+		(int)ctx->desc.viewport_h, ctx->max_ray_samples, ctx->part_prm.lifetime, ctx->part, ctx->part_count, ctx->draw_acc, s));
+	return FX_OK;
+}
+
+int fx_draw_particles(fx_ctx* ctx, void* stream, uint8_t frame_index)
+{
+	if (const int rc = draw_guard(ctx)) return rc;
+	if (frame_index >= FX_FRAME_COUNT) return FX_E_INVALID;
+	if (!ctx->draw_acc || !ctx->view_valid) return FX_E_STATE;
+	DeviceGuard dg(ctx->device);
+	hipStream_t s = pick_stream(ctx, stream);
+	ScopedMark mk(ctx, s, MK_RESOLVE);
+	if (const int rc = draw_splat(ctx, s)) return rc;
+	FX_HIP(launch_draw_resolve(ctx->draw, (int)ctx->desc.viewport_w, (int)ctx->desc.viewport_h, ctx->draw_acc, ctx->target, ctx->target_float, s));
+	return FX_OK;
+}
+
+// The splat alone, the accumulator copied out and cleared again; blocks.  (The stage buffer is not used: the copy goes straight to the caller.)
+int fx_particle_splats(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes)
+{
+	if (const int rc = draw_guard(ctx)) return rc;
+	if (!out || bytes != (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h * 2 * sizeof(uint64_t)) return FX_E_INVALID;
+	if (!ctx->draw_acc || !ctx->view_valid) return FX_E_STATE;
+	DeviceGuard dg(ctx->device);
+	hipStream_t s = pick_stream(ctx, stream);
+	{
+		ScopedMark mk(ctx, s, MK_RESOLVE);                                  // (the splat's time apart from the resolve's: tools/particle_draw_bench.py)
+		if (const int rc = draw_splat(ctx, s)) return rc;
+	}
+	FX_HIP(hipMemcpyAsync(out, ctx->draw_acc, bytes, hipMemcpyDeviceToHost, s));
+	FX_HIP(hipMemsetAsync(ctx->draw_acc, 0, bytes, s));
+	FX_HIP(hipStreamSynchronize(s));
 	return FX_OK;
 }
 

@@ -744,6 +744,43 @@ class Fluid:
         capi.check(self._lib.fx_particle_spawn_info(self._ctx, stream, C.byref(r)), "ParticleSpawnInfo")
         return {"born": int(r.born), "dropped": int(r.dropped), "blocked": int(r.blocked), "serial": [int(v) for v in r.serial]}
 
+    def SetParticleDraw(self, color, end_color=None, flags=0):
+        """the particle draw (fx_set_particle_draw): DrawParticles then splats every live particle onto the render target as an emissive point of
+        `color` (r, g, b, intensity), fading linearly to `end_color` (default: `color`) as its age reaches the lifetime of SetParticleParams,
+        dimmed by the smoke the direct view march shows in front of it.  Allocates two uint64 per pixel.  SetParticleDraw(None) switches it off
+        (the default) and frees that.  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole 3-D grids with a viewport only."""
+        self._need()
+        if color is None:
+            capi.check(self._lib.fx_set_particle_draw(self._ctx, None), "SetParticleDraw")
+            return
+        d = capi.ParticleDraw()
+        d.struct_size, d.flags = C.sizeof(capi.ParticleDraw), int(flags)
+        d.color = (C.c_float * 4)(*[float(v) for v in color])
+        d.end_color = (C.c_float * 4)(*[float(v) for v in (color if end_color is None else end_color)])
+        capi.check(self._lib.fx_set_particle_draw(self._ctx, C.byref(d)), "SetParticleDraw")
+
+    def GetParticleDraw(self):
+        """the setting in force (fx_get_particle_draw) as a dict with SetParticleDraw's keys; off: both colours 0"""
+        self._need()
+        d = capi.ParticleDraw()
+        capi.check(self._lib.fx_get_particle_draw(self._ctx, C.byref(d)), "GetParticleDraw")
+        return {"color": tuple(d.color), "end_color": tuple(d.end_color), "flags": d.flags}
+
+    def DrawParticles(self, frameIndex=0, stream=None):
+        """the particles onto the render target (fx_draw_particles), on top of what Render and RenderCube put there, with the camera of the
+        last UpdateFrame; FIELD_TARGET_FLOAT then holds the light added per pixel.  Enqueues only"""
+        self._need()
+        capi.check(self._lib.fx_draw_particles(self._ctx, stream, frameIndex), "DrawParticles")
+
+    def ParticleSplats(self, stream=None):
+        """the splat alone (fx_particle_splats; blocks): numpy uint64 [H][W][2], the young and the old amounts per pixel, 2^37 in total per
+        unoccluded particle whose footprint is on screen"""
+        self._need()
+        W, H = self.viewport
+        out = np.empty((H, W, 2), np.uint64)
+        capi.check(self._lib.fx_particle_splats(self._ctx, stream, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "ParticleSplats")
+        return out
+
     def SetParticlePool(self, n, stream=None):
         """a set of `n` dead records (0, 0, 0, -1) (SetParticles): how a set that is only ever spawned into starts"""
         rec = np.zeros((int(n), 4), np.float32)

@@ -631,8 +631,7 @@ int fx_heat(fx_ctx* ctx, void* stream);
  * call but the three getters) a context that owns fewer planes than the grid -- slab ranks of every transport, on the confinement's footing;
  * the getters succeed there and report the empty default, as fx_get_emitters does.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts.  FX_E_NOMEM:
  * the buffer cannot be allocated.
- * Out of scope: drawing
- * particles in the library's renders (births on the device: fx_set_particle_spawners below); momentum deposit, i.e. drag back on the flow (smoke and heat the particles do leave behind:
+ * Out of scope (drawing the particles: fx_set_particle_draw below; births on the device: fx_set_particle_spawners below): momentum deposit, i.e. drag back on the flow (smoke and heat the particles do leave behind:
  * fx_set_particle_trail below); sampling colour or temperature at points. */
 #define FX_MAX_PARTICLES      (1u << 26)
 #define FX_PARTICLES_DEVICE   0x1u      /* the pointer(s) are device memory of the context's device */
@@ -739,7 +738,8 @@ int fx_particle_order_device(fx_ctx* ctx, void** order_u32, void** live_u32);
  * rate < 0, bytes != X * Y * Z * 8, and (all but fx_get_particle_trail, which reports the default there) slab ranks.  FX_E_STATE:
  * FX_FLAG_RENDER_ONLY contexts; fx_deposit_particles and fx_particle_density while no trail is set.  FX_E_NOMEM: the accumulator cannot be
  * allocated.
- * Out of scope: per-particle strength or fading by age (the record has no room for it); momentum deposit; drawing; slab contexts (births: fx_set_particle_spawners below);
+ * Out of scope: per-particle strength or fading by age (the record has no room for it); momentum deposit; slab contexts (births: fx_set_particle_spawners,
+ * drawing: fx_set_particle_draw, both below);
  * restricting the apply pass to the set's bounding box; checkpointing. */
 typedef struct fx_particle_trail {
 	uint32_t struct_size, flags;   /* sizeof(fx_particle_trail) = 32; flags: 0 */
@@ -799,7 +799,8 @@ int fx_particle_density(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes);
  * fx_get_particle_spawners and fx_particle_spawn_info, which report the empty default there) slab ranks.  FX_E_STATE: FX_FLAG_RENDER_ONLY
  * contexts; fx_spawn_particles while no spawners are set.  FX_E_NOMEM: the block cannot be allocated.
  * (struct fx_particle_spawn_info has no typedef, as fx_particle_sort_info has none.)
- * Out of scope: initial velocities (the record has no room for them); per-spawner lifetimes; Gaussian shapes; drawing; slab contexts. */
+ * Out of scope: initial velocities (the record has no room for them); per-spawner lifetimes; Gaussian shapes; slab contexts (drawing:
+ * fx_set_particle_draw below). */
 #define FX_MAX_PARTICLE_SPAWNERS 16u
 #define FX_SPAWN_BOX  0u
 #define FX_SPAWN_BALL 1u     /* an ellipsoid with the half extents as semi-axes */
@@ -815,6 +816,65 @@ int fx_set_particle_spawners(fx_ctx* ctx, const fx_particle_spawner* list, uint3
 int fx_get_particle_spawners(fx_ctx* ctx, fx_particle_spawner* out, uint32_t capacity, uint32_t* count);
 int fx_spawn_particles(fx_ctx* ctx, void* stream);
 int fx_particle_spawn_info(fx_ctx* ctx, void* stream, struct fx_particle_spawn_info* out);
+
+/* The particle draw (no reference counterpart): the tracer particles as emissive points on the render target, each dimmed by the smoke between
+ * the eye and it.  A scene depth buffer hides an ember behind a wall; it does not dim one behind the plume -- that dimming is the alpha the view
+ * march accumulates in front of the particle, and the march, the colour field and the camera live here.  While a draw is set,
+ * fx_draw_particles splats every live record onto the render target, on top of what fx_render and fx_render_cube put there, attenuated by
+ * exactly the opacity the direct view march shows in front of a scene point at the particle's place.  The trail's recipe: an integer scatter,
+ * exact and independent of order, then one pass that turns integers into floats -- the same bits on every run.  Two launches
+ * (fx_particle_draw.hip): k_draw_splat over the records, k_draw_resolve over the pixels.  Off by default: a context that never calls the setter
+ * launches, computes and counts what it did before.
+ * The rule, fp32, every operation rounded as written, fma only where it says so (tests/particle_draw_ref.py restates it in numpy); (W, H) = the
+ * viewport, M = the forward WorldViewProj rows of the last fx_update_frame that carried matrices, ns = max_ray of fx_set_max_samples (the
+ * merged direct march's sample count), c(v) = fminf(fmaxf(v, 0), 1).  A record (p, age) is drawn iff age >= 0 (the move's test: -0.0 is live,
+ * a NaN is dead).
+ *   project    q_a = fma(c(p_a), 2, -1);  h_r = fma(1, M[4r+3], fma(q_z, M[4r+2], fma(q_y, M[4r+1], q_x * M[4r+0])));  culled unless h_3 > 0;
+ *              cx = h_0 / h_3, cy = h_1 / h_3, cz = h_2 / h_3;  culled unless 0 <= cz && cz < 1;  u = fma(cx, .5, .5), v = -fma(cy, .5, .5) + 1;
+ *              X = u * W, Y = v * H;  culled unless 0 <= X && X < W && 0 <= Y && Y < H -- every test is written so that a NaN culls;
+ *              the host pixel (px, py) = ((int)X, (int)Y)
+ *   depth      with a scene depth attached (fx_set_scene_depth): culled unless cz <= depth[py][px]
+ *   occlusion  the alpha sa of the direct view march of the host pixel, ended at the particle: the pixel's ray as fx_render casts it (sa = 0
+ *              where that discards), tMax = the ray parameter of the clip-space point (pixel centre, cz) as the depth-aware march forms it, and
+ *              the march's loop over ns samples with what alpha does not depend on left out: no light map, no light rays, no colour channels.
+ *              T = c(-sa + 1).  By construction sa is what the merged direct march returns as alpha with a depth buffer holding cz at that pixel
+ *   amounts    qb = (uint32)(T * 32768.0f + 0.5f);  s = lifetime > 0 ? c(age / lifetime) : 0 (fx_particle_params.lifetime);
+ *              qs = (uint32)(s * 256.0f + 0.5f);  young = qb * (256 - qs), old = qb * qs
+ *   footprint  bilinear over the four pixels whose centres surround (X, Y).  Per axis: t = X - 0.5, fl = floorf(t), w1 = (int)rintf((t - fl) * 128),
+ *              w0 = 128 - w1 on the pixels (int)fl and (int)fl + 1.  A footprint pixel outside the viewport is dropped, not clamped: light that
+ *              leaves the screen is lost.  acc[iy][ix][0] += young * wx * wy, acc[iy][ix][1] += old * wx * wy in uint64 (adds of 0 may be
+ *              skipped): qb << 22 in total for a footprint on screen, at most 2^37 a word, so FX_MAX_PARTICLES records cannot overflow one
+ *   resolve    per pixel:  Yv = (float)acc0 * 0x1p-37f, Ov = (float)acc1 * 0x1p-37f (one round-to-nearest-even conversion, then an exact scaling);
+ *              k0_c = color[c] * color[3], k1_c = end_color[c] * end_color[3];  src_c = fma(Ov, k1_c, Yv * k0_c) for c = r, g, b.  Where
+ *              acc0 | acc1 is non-zero the target takes the premultiplied blend of (src, alpha 0) -- additive, the target's alpha stays --,
+ *              FX_FIELD_TARGET_FLOAT = (src, 0) and both words go back to 0; elsewhere the target is not stored and FX_FIELD_TARGET_FLOAT = 0
+ * No value reaches an index unclamped or untested: whatever the caller wrote into the record buffer is safe to draw.
+ * fx_set_particle_draw with a struct allocates the accumulator, two uint64 per pixel (W * H * 16 bytes), zeroed, and the render target where
+ * no render has allocated it yet; FX_E_NOMEM if that fails, the previous state staying in force.  NULL = off (the default), which frees the
+ * accumulator.  All allocation and waiting happens here: fx_draw_particles only enqueues its two launches and stays capturable.
+ * fx_draw_particles draws the set in force with the camera of the last fx_update_frame that carried matrices, through the colour field
+ * fx_render marches (every sample gathers: FX_OPT_RENDER_ACCEL does not change a bit of it).  With no set of particles: FX_OK, the target
+ * untouched, FX_FIELD_TARGET_FLOAT all zero.  Timing: booked into fx_timing.resolve_ms; it does not count as a render.
+ * fx_particle_splats is the inspection call, the counterpart of fx_particle_density: it runs the splat alone on the set in force, copies the
+ * accumulator to out = uint64[H][W][2], clears it and blocks.  With no set: zeros.
+ * fx_get_particle_draw: the setting in force; off reports both colours 0.
+ * Configuration on the emitters' terms: per context, kept across fx_update_frame, not checkpointed, not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx or out-pointer, a wrong struct_size, unknown flag bits, a non-finite or
+ * negative member, bytes != W * H * 16, a frame_index >= FX_FRAME_COUNT, and (all but fx_get_particle_draw, which reports the default there) a
+ * 2-D grid, a context without a viewport, a slab rank.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts, which have no particles; fx_draw_particles
+ * and fx_particle_splats while no draw is set or before an fx_update_frame gave a camera (as fx_render).  FX_E_NOMEM: the accumulator or the
+ * target cannot be allocated.
+ * Out of scope: sprites larger than the bilinear footprint; per-particle colour or strength (the record has no room for them); absorbing
+ * particles; lighting the particles from the light map; motion blur; drawing into the cube map; slab and render-only contexts; checkpointing. */
+typedef struct fx_particle_draw {
+	uint32_t struct_size, flags;   /* sizeof(fx_particle_draw) = 40; flags: 0 */
+	float color[4];                /* rgb x intensity (w) of a particle of age 0; finite, >= 0 */
+	float end_color[4];            /* ... of a particle of age >= lifetime (fx_particle_params); finite, >= 0 */
+} fx_particle_draw;
+int fx_set_particle_draw(fx_ctx* ctx, const fx_particle_draw* draw);
+int fx_get_particle_draw(fx_ctx* ctx, fx_particle_draw* out);
+int fx_draw_particles(fx_ctx* ctx, void* stream, uint8_t frame_index);
+int fx_particle_splats(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes);
 
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
