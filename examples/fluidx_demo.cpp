@@ -4,7 +4,7 @@
 //   hipcc -std=c++17 examples/fluidx_demo.cpp -o fluidx_demo -Lfluidx12_amd -lfluidx_hip -Wl,-rpath,$PWD/fluidx12_amd
 // Usage: fluidx_demo [-gridSize X Y Z] [-maxRaySamples N] [-maxLightSamples N] [-radiance cube.dds] [-frames N] [-screenshot out.png|out.ppm] [-resume in.fxck] [-checkpoint out.fxck] [-vorticity E]
 //        [-emitter CX CY CZ R]... [-noimpulse]     (smoke sources, fx_set_emitters: texture space [0,1]^3, with the built-in's colour and lift; -noimpulse: without the reference's own source)
-//        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; the demo does not draw the ball itself)
+//        [-obstacle CX CY CZ R]     (a solid ball the smoke flows around, fx_set_obstacles: texture space [0,1]^3; drawn only with -drawObstacle)
 //        [-obstacleVelocity VX VY VZ]     (the ball moves: each frame it is voxelised anew at c + v * t, stopping at the walls, under one body with that velocity,
 //                                          fx_set_obstacle_bodies: texture units per unit time; it then pushes the smoke in front of it and drags a wake)
 //        [-obstacleMesh]     (the ball is handed over as a triangle mesh, fx_set_obstacle_meshes: a UV sphere of 16 x 32 segments built once and voxelised on the
@@ -13,6 +13,8 @@
 //        [-advection maccormack|semi-lagrangian]     (the advection scheme, fx_set_advection_scheme; default: the reference's semi-Lagrangian step)
 //        [-multigrid]     (the pressure solve as two multigrid V(2,2) cycles instead of the Jacobi sweeps, fx_set_pressure_solver)
 //        [-light X Y Z] [-pointLight] [-lightColor R G B I] [-ambient R G B I]     (the scene light, fx_set_light: world space, the volume is [-10, 10]^3)
+//        [-drawObstacle [R G B]]     (the ball itself, ray-cast from the voxel mask and lit by the scene light before the volume is rendered, its depth
+//                                     attached so that the plume wraps around it, fx_set_obstacle_draw; albedo default 0.8 0.8 0.8, times 0.4; 3-D grids)
 //        [-embers N]     (N tracer particles born at the built-in impulse, fx_set_particle_spawners, and drawn on top of the volume as glowing points that
 //                         the smoke in front of them dims, fx_set_particle_draw; 3-D grids)
 // (FluidX12.cpp:398-433; the screen shot is a PNG like the reference's (FluidX12.cpp:640-660), written without a compression library, or a binary PPM by extension)
@@ -110,6 +112,8 @@ int main(int argc, char** argv)
 	float obstacle[4] = {};
 	bool obstacleMoves = false;
 	bool obstacleMesh = false;
+	bool drawObstacle = false;                          // not in the reference: nothing but the volume is drawn there
+	float obstacleAlbedo[4] = { 0.8f, 0.8f, 0.8f, 0.4f };   // (x 0.4: the reference's light is 3 pi + 1.5 pi strong)
 	float obstacleVelocity[3] = {};
 	uint32_t openWalls = 0;                             // not in the reference: its box is closed on all six faces
 	uint32_t advection = FX_ADVECT_SEMI_LAGRANGIAN;     // not in the reference: its advection is semi-Lagrangian
@@ -138,6 +142,12 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "-obstacle") && i + 4 < argc) { for (float& v : obstacle) v = (float)atof(argv[++i]); obstacleSet = true; }
 		else if (!std::strcmp(argv[i], "-obstacleVelocity") && i + 3 < argc) { for (float& v : obstacleVelocity) v = (float)atof(argv[++i]); obstacleMoves = true; }
 		else if (!std::strcmp(argv[i], "-obstacleMesh")) obstacleMesh = true;
+		else if (!std::strcmp(argv[i], "-drawObstacle")) {
+			drawObstacle = true;
+			char* end = nullptr;                            // three numbers may follow
+			if (i + 3 < argc && (std::strtod(argv[i + 1], &end), end != argv[i + 1] && !*end))
+				for (int c = 0; c < 3; ++c) obstacleAlbedo[c] = (float)atof(argv[++i]);
+		}
 		else if (!std::strcmp(argv[i], "-openWalls") && i + 1 < argc) openWalls = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
 		else if (!std::strcmp(argv[i], "-advection") && i + 1 < argc) {
 			const char* v = argv[++i];
@@ -231,6 +241,11 @@ int main(int argc, char** argv)
 	if (obstacleMesh && !obstacleSet) { std::fprintf(stderr, "-obstacleMesh: there is no -obstacle to hand over\n"); return 1; }
 	if (obstacleMoves && !obstacleSet) { std::fprintf(stderr, "-obstacleVelocity: there is no -obstacle to move\n"); return 1; }
 	if (obstacleSet && !placeObstacle(0.0f)) { std::fprintf(stderr, "-obstacle: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
+	if (drawObstacle && (!obstacleSet || grid.z <= 1)) { std::fprintf(stderr, "-drawObstacle: there is no -obstacle on a 3-D grid to draw\n"); return 1; }
+	if (drawObstacle && (!fluid.SetObstacleDraw(obstacleAlbedo) || !fluid.AttachObstacleDepth(1.0f, 1000.0f))) {   // (the projection's planes below)
+		std::fprintf(stderr, "-drawObstacle: %s\n", fx_error_string(fluid.LastStatus()));
+		return 1;
+	}
 	if (openWalls && !fluid.SetOpenWalls(openWalls)) { std::fprintf(stderr, "-openWalls 0x%x: %s\n", (unsigned)openWalls, fx_error_string(fluid.LastStatus())); return 1; }
 	if (advection != FX_ADVECT_SEMI_LAGRANGIAN && !fluid.SetAdvectionScheme(advection)) { std::fprintf(stderr, "-advection: %s\n", fx_error_string(fluid.LastStatus())); return 1; }
 	if (multigrid) {
@@ -275,6 +290,7 @@ int main(int argc, char** argv)
 		if (grid.z > 1) {
 			fluid.ClearRenderTarget(nullptr, clearColor);
 			if (radiance) probe.RenderEnvironment(fluid, nullptr, frameIndex);      // FluidX12.cpp:483: the sky first
+			if (drawObstacle) fluid.DrawObstacles(frameIndex);                      // the ball, and its depth for the marches that follow
 			fluid.Render(nullptr, frameIndex, Fluid::OPTIMIZED);                    // marches + renderCube onto the target
 			if (embers) fluid.DrawParticles(frameIndex);                            // the embers on top, dimmed by the smoke in front of them
 		}

@@ -121,6 +121,10 @@ class ParticleDraw(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("color", C.c_float * 4), ("end_color", C.c_float * 4)]
 
 
+class ObstacleDraw(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("albedo", C.c_float * 4)]
+
+
 class ParticleSpawnInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("born", C.c_uint64), ("dropped", C.c_uint64), ("blocked", C.c_uint64),
                 ("serial", C.c_uint64 * 16)]
@@ -204,6 +208,11 @@ SYMBOLS = {
     "fx_get_particle_draw": (C.c_int, [_vp, C.POINTER(ParticleDraw)]),
     "fx_draw_particles": (C.c_int, [_vp, _vp, C.c_uint8]),
     "fx_particle_splats": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.c_size_t]),
+    "fx_set_obstacle_draw": (C.c_int, [_vp, C.POINTER(ObstacleDraw)]),
+    "fx_get_obstacle_draw": (C.c_int, [_vp, C.POINTER(ObstacleDraw)]),
+    "fx_draw_obstacles": (C.c_int, [_vp, _vp, C.c_uint8, _vp]),
+    "fx_obstacle_depth_device": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
+    "fx_obstacle_hits": (C.c_int, [_vp, _vp, C.c_uint8, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_size_t]),
     "fx_set_open_walls": (C.c_int, [_vp, C.c_uint32]),
     "fx_get_open_walls": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "fx_open_inflow": (C.c_int, [_vp, _vp]),

@@ -130,7 +130,7 @@ public:
 	bool Emit(void* stream = nullptr) { m_status = fx_emit(m_ctx, stream); return m_status == FX_OK; }
 
 	// not in the reference (its only boundaries are the box's walls): voxelised solid obstacles the smoke flows around (fx_set_obstacles;
-	// mask uint8[Z][Y][X], non-zero = solid; nullptr detaches).  The caller draws the object itself and passes its depth with SetSceneDepth
+	// mask uint8[Z][Y][X], non-zero = solid; nullptr detaches).  Drawing the solids: SetObstacleDraw below
 	bool SetObstacles(const uint8_t* solid, size_t bytes, void* stream = nullptr, bool deviceMemory = false)
 	{
 		m_status = fx_set_obstacles(m_ctx, stream, solid, bytes, deviceMemory ? FX_OBSTACLES_DEVICE : 0u);
@@ -175,6 +175,36 @@ public:
 		m.vertex_count = (uint32_t)(positions.size() / 3); m.triangle_count = (uint32_t)(indices.size() / 3);
 		m.transform = transform;
 		return SetObstacleMeshes(&m, 1, report, stream);
+	}
+
+	// not in the reference: the obstacle draw -- the solid cells of the mask ray-cast into the render target, lit by the scene light, and into a
+	// depth buffer (fx_set_obstacle_draw: albedo rgb x intensity; nullptr = off, the default), the draw itself in front of Render
+	// (fx_draw_obstacles; sceneDepthDevice: the caller's own scene or nullptr), its depth buffer attached as the scene depth of the following
+	// renders (fx_obstacle_depth_device + fx_set_scene_depth) and the cast alone copied to the host (fx_obstacle_hits: uint64[H][W], float[H][W])
+	bool SetObstacleDraw(const fx_obstacle_draw* draw) { m_status = fx_set_obstacle_draw(m_ctx, draw); return m_status == FX_OK; }
+	bool SetObstacleDraw(const float albedo[4])
+	{
+		const fx_obstacle_draw d = { (uint32_t)sizeof(fx_obstacle_draw), 0u, { albedo[0], albedo[1], albedo[2], albedo[3] } };
+		return SetObstacleDraw(&d);
+	}
+	bool GetObstacleDraw(fx_obstacle_draw& out) { m_status = fx_get_obstacle_draw(m_ctx, &out); return m_status == FX_OK; }
+	bool DrawObstacles(uint8_t frameIndex = 0, const float* sceneDepthDevice = nullptr, void* stream = nullptr)
+	{
+		m_status = fx_draw_obstacles(m_ctx, stream, frameIndex, sceneDepthDevice);
+		return m_status == FX_OK;
+	}
+	bool AttachObstacleDepth(float zNear = 1.0f, float zFar = 1000.0f, void* stream = nullptr)
+	{
+		void* depth = nullptr;
+		m_status = fx_obstacle_depth_device(m_ctx, &depth);
+		if (m_status == FX_OK && !depth) m_status = FX_E_STATE;
+		if (m_status == FX_OK) m_status = fx_set_scene_depth(m_ctx, stream, static_cast<const float*>(depth), m_width, m_height, zNear, zFar, FX_DEPTH_DEVICE);
+		return m_status == FX_OK;
+	}
+	bool ObstacleHits(uint64_t* hits, float* depth, size_t pixels, uint8_t frameIndex = 0, const float* sceneDepthDevice = nullptr, void* stream = nullptr)
+	{
+		m_status = fx_obstacle_hits(m_ctx, stream, frameIndex, sceneDepthDevice, hits, depth, pixels);
+		return m_status == FX_OK;
 	}
 
 	// not in the reference (its box is closed): the faces through which the smoke leaves (fx_set_open_walls; FX_WALL_* bits, 0 = all closed,

@@ -89,7 +89,7 @@ void free_all(fx_ctx* c)
 		if (c->p[i]) (void)hipFree(c->p[i]);
 	}
 	void* others[] = { c->env, c->cube_depth, c->depth_own, c->accel.occ, c->accel.alpha, c->accel.bits, c->accel.list, c->accel.cells, c->accel.gi, c->accel.ctr, c->target, c->target_float, c->p_face[0], c->p_face[1], c->b, c->frozen, c->frozen_alt, c->lightmap, c->cube, c->sh_dev, c->halo_overflow, c->stage,
-		c->sh_scratch[0], c->sh_scratch[1], c->sh_scratch[2], c->sh_scratch[3], c->p_aux, c->fz_mask[0], c->fz_mask[1], c->fz_mask[2], c->fz_tile_next, c->fz_stat, c->fz_list[0], c->fz_list[1], c->fz_counts, c->sample_counters, c->adv_far, c->obst_code, c->obst_spare, c->obst_stats, c->vox_bits, c->vox_report, c->vox_work, c->temp[0], c->temp[1], c->mc_vel, c->mc_col, c->mg_mem, c->part, c->psort_mem, c->trail_acc, c->spawn_mem, c->draw_acc };
+		c->sh_scratch[0], c->sh_scratch[1], c->sh_scratch[2], c->sh_scratch[3], c->p_aux, c->fz_mask[0], c->fz_mask[1], c->fz_mask[2], c->fz_tile_next, c->fz_stat, c->fz_list[0], c->fz_list[1], c->fz_counts, c->sample_counters, c->adv_far, c->obst_code, c->obst_spare, c->obst_stats, c->vox_bits, c->vox_report, c->vox_work, c->temp[0], c->temp[1], c->mc_vel, c->mc_col, c->mg_mem, c->part, c->psort_mem, c->trail_acc, c->spawn_mem, c->draw_acc, c->odraw_depth, c->odraw_bricks };
 	for (void* q : others) if (q) (void)hipFree(q);
 	for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
 	if (c->step_rec) (void)hipFree(c->step_rec);

@@ -126,6 +126,13 @@ struct fx_ctx {
 	// allocated and freed by fx_set_particle_draw alone
 	fx_particle_draw draw = { (uint32_t)sizeof(fx_particle_draw), 0u, { 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f, 0.0f } };
 	unsigned long long* draw_acc = nullptr;    // device; null = no draw: every call is the one it is without the feature
+	// the obstacle draw (fx_set_obstacle_draw; fx_obstacle_draw.hip): while set, the depth-out buffer (float per pixel of the viewport) and the brick
+	// volume of the code volume (fx::obstacle_brick_count words); allocated and freed by fx_set_obstacle_draw alone
+	fx_obstacle_draw odraw = { (uint32_t)sizeof(fx_obstacle_draw), 0u, { 0.0f, 0.0f, 0.0f, 0.0f } };
+	float* odraw_depth = nullptr;   // device; null = no draw: every call is the one it is without the feature
+	unsigned long long* odraw_bricks = nullptr;
+	uint64_t obst_gen = 0;          // counts the changes of the mask in force (the mask setters, the detach)
+	uint64_t odraw_packed = 0;      // obst_gen of the mask the brick volume was last packed from (the draw packs when they differ)
 	// the scene light (fx_set_light; render state like the scene depth): position, colour and ambient live in `fc` (light_pt, light_color,
 	// ambient), which fx_create fills with the reference's constants and fx_update_frame leaves alone
 	uint32_t light_kind = 0;        // FX_LIGHT_DIRECTIONAL / FX_LIGHT_POINT: which instantiation of the light-ray kernels a render launches

@@ -224,7 +224,18 @@ hipError_t launch_trail_apply(const Geom& g, int half_store, const fx_particle_t
 hipError_t launch_draw_splat(const Geom& g, int half_store, const void* color, const FrameConsts& fc, const float wvp[16], const float* depth, int W, int H,
 	uint32_t ns, float lifetime, const float* records, uint32_t count, unsigned long long* acc, hipStream_t s);
 hipError_t launch_draw_resolve(const fx_particle_draw& dr, int W, int H, unsigned long long* acc, uint8_t* target, float* out_float, hipStream_t s);
-// ---- the particle spawners (fx_particle_spawn.hip; fx_set_particle_spawners, fx_spawn_particles).  One device block: SpawnState at its head,
+// ---- the obstacle draw (fx_obstacle_draw.hip; fx_set_obstacle_draw, fx_draw_obstacles, fx_obstacle_hits).  bricks: one uint64 per 4 x 4 x 4
+// cells, bit (z & 3) * 16 + (y & 3) * 4 + (x & 3) = the cell is solid (code bit 6), cells beyond the grid 0; brick (bx, by, bz) at
+// (bz * BY + by) * BX + bx with B_a = (N_a + 3) / 4.  pack: the brick volume of `code`.  cast: per pixel of the W x H viewport the view ray walked
+// to the first solid cell of `code` (null: every pixel misses) within the box [lo, hi); target, out_float, depth_out (float[H][W]) and hits
+// (uint64[H][W]) are each stored unless null; scene: the caller's depth float[H][W] or null, never depth_out.  hipErrorInvalidValue for a 2-D grid
+// or one of 2^32 cells or more.  Both enqueue only
+inline size_t obstacle_brick_count(const Geom& g) { return (size_t)((g.X + 3) / 4) * (size_t)((g.Y + 3) / 4) * (size_t)((g.Zg + 3) / 4); }
+hipError_t launch_obstacle_pack(const Geom& g, const uint8_t* code, unsigned long long* bricks, hipStream_t s);
+hipError_t launch_obstacle_cast(const Geom& g, const uint8_t* code, const unsigned long long* bricks, const int lo[3], const int hi[3],
+	const FrameConsts& fc, const float wvp[16], int point_light, const fx_obstacle_draw& dr, const float* scene, int W, int H,
+	uint8_t* target, float* out_float, float* depth_out, unsigned long long* hits, hipStream_t s);
+// ---- the particle spawners (fx_particle_spawn.hip;fx_set_particle_spawners, fx_spawn_particles).  One device block: SpawnState at its head,
 // then one count of dead records per workgroup of kSpawnRecords records and the scan's block sums, laid out by spawn_plan(count).  The setter
 // fills `site` and zeroes the rest; born .. serial are what fx_particle_spawn_info copies out in one piece
 const uint32_t kSpawnThreads = 256;                           // threads of a count / place workgroup

@@ -484,8 +484,10 @@ __device__ __forceinline__ void flush_counts(unsigned long long* __restrict__ co
 }
 
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool compute_ray_origin(float o[3], const float d[3])   // RayMarch.hlsli:146-173
+// axis: the axis whose quotient became U, -1 where there is none (the origin lies inside the box, or no face is hit); the obstacle draw's entry face
+__device__ __forceinline__ bool compute_ray_origin(float o[3], const float d[3], int& axis)   // RayMarch.hlsli:146-173
 {
+	axis = -1;
 	if (fabsf(o[0]) <= 1.0f && fabsf(o[1]) <= 1.0f && fabsf(o[2]) <= 1.0f) return true;
 	float U = 3.40282347e+38f;
 	bool hit = false;
@@ -497,12 +499,13 @@ __device__ __forceinline__ bool compute_ray_origin(float o[3], const float d[3])
 		const int j = (i + 1) % 3, k = (i + 2) % 3;
 		if (!(1.0f >= fabsf(fmaf(d[j], u, o[j])))) continue;
 		if (!(1.0f >= fabsf(fmaf(d[k], u, o[k])))) continue;
-		if (u < U) { U = u; hit = true; }
+		if (u < U) { U = u; hit = true; axis = i; }
 	}
 #pragma unroll
 	for (int a = 0; a < 3; ++a) o[a] = fminf(fmaxf(fmaf(d[a], U, o[a]), -1.0f), 1.0f);
 	return hit;
 }
+__device__ __forceinline__ bool compute_ray_origin(float o[3], const float d[3]) { int axis; return compute_ray_origin(o, d, axis); }
 
 __device__ __forceinline__ uint32_t to_unorm8(float v)
 {
@@ -708,8 +711,8 @@ __device__ __forceinline__ bool cube_texel_ray(const FrameConsts& fc, int face, 
 	return true;
 }
 
-// screen pixel -> ray (PSRayCast.hlsl:17-26,47-50); false = discard
-__device__ __forceinline__ bool pixel_ray(const FrameConsts& fc, int px, int py, int W, int H, float o[3], float d[3])
+// screen pixel -> ray (PSRayCast.hlsl:17-26,47-50); false = discard.  axis: compute_ray_origin's
+__device__ __forceinline__ bool pixel_ray(const FrameConsts& fc, int px, int py, int W, int H, float o[3], float d[3], int& axis)
 {
 	const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H;
 	const float qx = fmaf(u, 2.0f, -1.0f), qy = fmaf(v, -2.0f, 1.0f);
@@ -725,7 +728,12 @@ __device__ __forceinline__ bool pixel_ray(const FrameConsts& fc, int px, int py,
 	}
 	const float rl = rsqf(dot3(d[0], d[1], d[2], d[0], d[1], d[2]));
 	d[0] *= rl; d[1] *= rl; d[2] *= rl;
-	return compute_ray_origin(o, d);                                               // :50 discard
+	return compute_ray_origin(o, d, axis);                                         // :50 discard
+}
+__device__ __forceinline__ bool pixel_ray(const FrameConsts& fc, int px, int py, int W, int H, float o[3], float d[3])
+{
+	int axis;
+	return pixel_ray(fc, px, py, W, H, o, d, axis);
 }
 
 // ---- scene depth (the reference's _HAS_DEPTH_MAP_ variants; fx_set_scene_depth) ------------------------------------------------

@@ -1,5 +1,5 @@
 // fx_stage_api.cpp -- the entry points of the step's optional stages (include/fluidx_hip.h): vorticity confinement, emitters, obstacles with
-// their bodies and meshes, open walls, buoyancy, tracer particles with their sort, trail, spawners and draw, the advection scheme and the pressure solver --
+// their bodies and meshes, open walls, buoyancy, tracer particles with their sort, trail, spawners and draw, the obstacle draw, the advection scheme and the pressure solver --
 // each stage's setter, getter and its phase of the step (fx_schedule.cpp) on its own.  A setter that owns device memory builds the new
 // buffers beside the ones in force (DevBuf, fx_host.h) and commits in its last lines.  The per-frame calls: fx_api.cpp.
 #include "fx_host.h"
@@ -103,6 +103,7 @@ static int install_obstacle_mask(fx_ctx* ctx, const uint8_t* src, hipStream_t s)
 	FX_HIP(hipMemcpyAsync(st, ctx->obst_stats, sizeof st, hipMemcpyDeviceToHost, s));
 	FX_HIP(hipStreamSynchronize(s));                                        // the count and the box size the enforce launch; `solid` is free again
 	std::swap(ctx->obst_code, ctx->obst_spare);
+	++ctx->obst_gen;                                                        // (the obstacle draw packs its bricks anew)
 	ctx->obst_cells = (uint64_t)st[0] | ((uint64_t)st[1] << 32);
 	for (int a = 0; a < 3; ++a) {
 		ctx->obst_lo[a] = ctx->obst_cells ? (int)st[2 + a] : 0;
@@ -123,6 +124,7 @@ int fx_set_obstacles(fx_ctx* ctx, void* stream, const uint8_t* solid, size_t byt
 			std::swap(ctx->obst_spare, ctx->obst_code);
 		}
 		ctx->obst_cells = 0;
+		++ctx->obst_gen;
 		return FX_OK;
 	}
 	if (ctx->solver.kind == FX_PRESSURE_MULTIGRID) return FX_E_STATE;          // the multigrid solve has no coarse code volumes
@@ -655,6 +657,110 @@ int fx_particle_splats(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes)
 	}
 	FX_HIP(hipMemcpyAsync(out, ctx->draw_acc, bytes, hipMemcpyDeviceToHost, s));
 	FX_HIP(hipMemsetAsync(ctx->draw_acc, 0, bytes, s));
+	FX_HIP(hipStreamSynchronize(s));
+	return FX_OK;
+}
+
+// ---- the obstacle draw (fx_obstacle_draw.hip) --------------------------------------------------------------------
+// what its calls want beside sim_guard: a 3-D grid whose cell index fits the hits word, and a viewport to cast it onto
+static int odraw_guard(const fx_ctx* ctx)
+{
+	if (const int rc = sim_guard(ctx)) return rc;
+	if (ctx->g.Zg <= 1 || !ctx->desc.viewport_w || !ctx->desc.viewport_h) return FX_E_INVALID;
+	if (ctx->g.cells_owned() >= ((size_t)1 << 32)) return FX_E_INVALID;
+	return FX_OK;
+}
+
+// The depth-out buffer, filled with 1.0, and the brick volume are allocated by the first call that sets a draw and freed by NULL; a later call
+// replaces the albedo and keeps them.  The render target too, where no render has allocated it yet.  Blocks.
+int fx_set_obstacle_draw(fx_ctx* ctx, const fx_obstacle_draw* d)
+{
+	if (const int rc = odraw_guard(ctx)) return rc;
+	DeviceGuard dg(ctx->device);
+	if (!d) {
+		const int freed = dev_free(ctx, &ctx->odraw_depth);                  // (waits for the device: no draw is in flight any more)
+		const int freed2 = dev_free(ctx, &ctx->odraw_bricks);
+		const fx_obstacle_draw off = { (uint32_t)sizeof(fx_obstacle_draw), 0u, { 0.0f, 0.0f, 0.0f, 0.0f } };
+		ctx->odraw = off;
+		return freed ? freed : freed2;
+	}
+	if (d->struct_size != sizeof(fx_obstacle_draw) || d->flags != 0) return FX_E_INVALID;
+	for (int a = 0; a < 4; ++a) if (!std::isfinite(d->albedo[a]) || d->albedo[a] < 0.0f) return FX_E_INVALID;
+	DevBuf depth, bricks;
+	if (!ctx->odraw_depth) {
+		const size_t pixels = (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h;
+		if (const int rc = depth.alloc(ctx, pixels * sizeof(float))) return rc;
+		if (const int rc = bricks.alloc(ctx, obstacle_brick_count(ctx->g) * sizeof(unsigned long long))) return rc;
+		FX_HIP(hipMemsetD32Async((hipDeviceptr_t)depth.get(), 0x3F800000, pixels, ctx->stream));   // 1.0f: nothing there
+	}
+	if (const int rc = ensure_target(ctx, ctx->stream)) return rc;
+	FX_HIP(hipStreamSynchronize(ctx->stream));
+	if (depth.get()) {
+		ctx->odraw_depth = depth.release<float>();
+		ctx->odraw_bricks = bricks.release<unsigned long long>();
+		ctx->odraw_packed = ctx->obst_gen - 1;                               // nothing is packed yet: the first draw packs
+	}
+	ctx->odraw = *d;
+	return FX_OK;
+}
+
+int fx_get_obstacle_draw(fx_ctx* ctx, fx_obstacle_draw* out) { return get_setting(ctx, &fx_ctx::odraw, out); }
+
+int fx_obstacle_depth_device(fx_ctx* ctx, void** depth)
+{
+	if (const int rc = sim_guard(ctx, false)) return rc;
+	if (!depth) return FX_E_INVALID;
+	*depth = ctx->odraw_depth;
+	return FX_OK;
+}
+
+// what fx_draw_obstacles and fx_obstacle_hits share: the arguments' status ...
+static int odraw_status(const fx_ctx* ctx, uint8_t frame_index, const float* scene)
+{
+	if (const int rc = odraw_guard(ctx)) return rc;
+	if (frame_index >= FX_FRAME_COUNT) return FX_E_INVALID;
+	if (!ctx->odraw_depth || !ctx->view_valid) return FX_E_STATE;
+	if (scene && scene == ctx->odraw_depth) return FX_E_INVALID;
+	return FX_OK;
+}
+
+// ... and the launches: the pack where the mask has changed since the last one, then the cast
+static int odraw_cast(fx_ctx* ctx, hipStream_t s, const float* scene, uint8_t* target, float* out_float, float* depth_out, unsigned long long* hits)
+{
+	const uint8_t* code = ctx->obst_code;
+	if (code && ctx->odraw_packed != ctx->obst_gen) {
+		FX_HIP(launch_obstacle_pack(ctx->g, code, ctx->odraw_bricks, s));
+		ctx->odraw_packed = ctx->obst_gen;
+	}
+	FX_HIP(launch_obstacle_cast(ctx->g, code, ctx->odraw_bricks, ctx->obst_lo, ctx->obst_hi, ctx->fc, ctx->wvp, ctx->light_kind == FX_LIGHT_POINT,
+		ctx->odraw, scene, (int)ctx->desc.viewport_w, (int)ctx->desc.viewport_h, target, out_float, depth_out, hits, s));
+	return FX_OK;
+}
+
+int fx_draw_obstacles(fx_ctx* ctx, void* stream, uint8_t frame_index, const float* scene_depth_device)
+{
+	if (const int rc = odraw_status(ctx, frame_index, scene_depth_device)) return rc;
+	DeviceGuard dg(ctx->device);
+	hipStream_t s = pick_stream(ctx, stream);
+	ScopedMark mk(ctx, s, MK_RESOLVE);
+	return odraw_cast(ctx, s, scene_depth_device, ctx->target, ctx->target_float, ctx->odraw_depth, nullptr);
+}
+
+// The cast alone into the staging buffer, hits words and depths copied out; blocks
+int fx_obstacle_hits(fx_ctx* ctx, void* stream, uint8_t frame_index, const float* scene_depth_device, uint64_t* hits_out, float* depth_out, size_t pixels)
+{
+	if (const int rc = odraw_guard(ctx)) return rc;
+	if (pixels != (size_t)ctx->desc.viewport_w * ctx->desc.viewport_h) return FX_E_INVALID;
+	if (const int rc = odraw_status(ctx, frame_index, scene_depth_device)) return rc;
+	DeviceGuard dg(ctx->device);
+	hipStream_t s = pick_stream(ctx, stream);
+	FX_HIP(hipDeviceSynchronize());                                          // (the staging buffer is shared with the context's other blocking calls)
+	if (const int rc = ensure_stage(ctx, pixels * (sizeof(uint64_t) + sizeof(float)))) return rc;
+	unsigned long long* hits = reinterpret_cast<unsigned long long*>(ctx->stage);
+	float* depth = reinterpret_cast<float*>(hits + pixels);
+	if (const int rc = odraw_cast(ctx, s, scene_depth_device, nullptr, nullptr, depth, hits)) return rc;
+	if (hits_out) FX_HIP(hipMemcpyAsync(hits_out, hits, pixels * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+	if (depth_out) FX_HIP(hipMemcpyAsync(depth_out, depth, pixels * sizeof(float), hipMemcpyDeviceToHost, s));
 	FX_HIP(hipStreamSynchronize(s));
 	return FX_OK;
 }

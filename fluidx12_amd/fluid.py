@@ -406,6 +406,78 @@ class Fluid:
         return [{"box_lo": tuple(b.box_lo), "box_hi": tuple(b.box_hi), "linear": tuple(b.linear), "angular": tuple(b.angular),
                  "pivot": tuple(b.pivot), "flags": b.flags} for b in arr[:n.value]]
 
+    def SetObstacleDraw(self, albedo, flags=0):
+        """the obstacle draw (fx_set_obstacle_draw): DrawObstacles then ray-casts the solid cells of the mask in force into the render target,
+        each visible face lit by the light of SetLight and coloured `albedo` (r, g, b, intensity), and into a depth buffer for
+        AttachObstacleDepth.  Allocates that buffer and one uint64 per 4 x 4 x 4 cells.  SetObstacleDraw(None) switches it off (the default)
+        and frees both -- detach the depth first.  Configuration: kept across UpdateFrame, not stored in checkpoints.  Whole 3-D grids with
+        a viewport only."""
+        self._need()
+        if albedo is None:
+            capi.check(self._lib.fx_set_obstacle_draw(self._ctx, None), "SetObstacleDraw")
+            return
+        d = capi.ObstacleDraw()
+        d.struct_size, d.flags = C.sizeof(capi.ObstacleDraw), int(flags)
+        d.albedo = (C.c_float * 4)(*[float(v) for v in albedo])
+        capi.check(self._lib.fx_set_obstacle_draw(self._ctx, C.byref(d)), "SetObstacleDraw")
+
+    def GetObstacleDraw(self):
+        """the setting in force (fx_get_obstacle_draw): {"albedo", "flags"}; off: albedo 0"""
+        self._need()
+        d = capi.ObstacleDraw()
+        capi.check(self._lib.fx_get_obstacle_draw(self._ctx, C.byref(d)), "GetObstacleDraw")
+        return {"albedo": tuple(d.albedo), "flags": d.flags}
+
+    @staticmethod
+    def _device_depth(scene_depth, w, h):
+        """the device pointer of an optional caller's scene depth: None, an integer address, or a contiguous float32[h][w] torch tensor"""
+        if scene_depth is None:
+            return None
+        if hasattr(scene_depth, "data_ptr"):
+            if tuple(scene_depth.shape) != (h, w) or str(scene_depth.dtype) != "torch.float32" or not scene_depth.is_contiguous():
+                raise ValueError("device depth must be a contiguous float32[%d][%d]" % (h, w))
+            return C.c_void_p(scene_depth.data_ptr())
+        return C.c_void_p(int(scene_depth))
+
+    def ObstacleDepthPointer(self):
+        """the device address of the draw's depth buffer, float32[H][W] (fx_obstacle_depth_device); None while the draw is off"""
+        self._need()
+        p = C.c_void_p()
+        capi.check(self._lib.fx_obstacle_depth_device(self._ctx, C.byref(p)), "ObstacleDepthPointer")
+        return p.value
+
+    def DrawObstacles(self, frameIndex=0, scene_depth=None, stream=None):
+        """the solids onto the render target and into the draw's depth buffer (fx_draw_obstacles), before Render, with the camera of the last
+        UpdateFrame; FIELD_TARGET_FLOAT then holds (colour, 1) per drawn pixel.  scene_depth: the caller's own scene, a float32[H][W] torch
+        tensor on the context's device (or its address); a solid behind it is not drawn.  Enqueues only"""
+        self._need()
+        w, h = self.viewport
+        capi.check(self._lib.fx_draw_obstacles(self._ctx, stream, frameIndex, self._device_depth(scene_depth, w, h)), "DrawObstacles")
+
+    def AttachObstacleDepth(self, z_near=1.0, z_far=1000.0, stream=None):
+        """the draw's depth buffer as the scene depth of the following renders (fx_set_scene_depth, FX_DEPTH_DEVICE): the marches end at
+        the solids, DrawParticles culls what lies behind them.  Read in place: every DrawObstacles on the same stream refreshes it.
+        SetSceneDepth(None) detaches"""
+        self._need()
+        p = self.ObstacleDepthPointer()
+        if not p:
+            raise capi.FluidxError(capi.FX_E_STATE, "AttachObstacleDepth")
+        w, h = self.viewport
+        capi.check(self._lib.fx_set_scene_depth(self._ctx, stream, C.c_void_p(p), w, h, float(z_near), float(z_far), capi.DEPTH_DEVICE),
+                   "AttachObstacleDepth")
+        self._depth_ref = None
+
+    def ObstacleHits(self, frameIndex=0, scene_depth=None, stream=None):
+        """the cast alone (fx_obstacle_hits; blocks) -> (uint64[H][W], float32[H][W]): per pixel the hits word -- bit 63 = the walk hit,
+        bit 62 = drawn, bits 32-34 = the face (2 axis + (step > 0); 6 = the eye's own cell), bits 0-31 = the cell (z Y + y) X + x -- and
+        the depth DrawObstacles would store"""
+        self._need()
+        w, h = self.viewport
+        hits, depth = np.empty((h, w), np.uint64), np.empty((h, w), np.float32)
+        capi.check(self._lib.fx_obstacle_hits(self._ctx, stream, frameIndex, self._device_depth(scene_depth, w, h),
+                                              hits.ctypes.data_as(C.POINTER(C.c_uint64)), _fp(depth), hits.size), "ObstacleHits")
+        return hits, depth
+
     def SetOpenWalls(self, faces):
         """the faces of the box through which the smoke leaves (fx_set_open_walls): a set of capi.WALL_* bits, 0 = all closed (default).  Beyond
         an open face the pressure is 0, the smoke is clear air and the temperature ambient; the projection does not damp flow towards it.

@@ -368,7 +368,9 @@ int fx_emit(fx_ctx* ctx, void* stream);
  * With an all-zero mask the three stages are, operation for operation, the plain ones (tests/obstacle_ref/ restates all four in C++).
  * The stages read one code byte per cell, built on the device once per call (one upload + one launch: a moving obstacle is a new call per
  * frame); the pressure solve then runs one obstacle-aware sweep per launch and ignores FX_FLAG_JACOBI_FUSE_MASK.
- * Rendering is unchanged: a solid cell holds no smoke; the caller draws the object and passes its depth with fx_set_scene_depth.
+ * The marches are unchanged: a solid cell holds no smoke.  The solids themselves are drawn by fx_set_obstacle_draw / fx_draw_obstacles below, which
+ * ray-cast the mask into the render target and a depth buffer for fx_set_scene_depth; a caller with a rasteriser of its own may still draw the
+ * object itself and pass its depth.
  * fx_set_obstacles: replaces the previous mask; NULL detaches (`bytes` is ignored): every call behaves exactly as without this function.  An
  * all-zero mask is legal and keeps the obstacle kernels in force.  flags & FX_OBSTACLES_DEVICE: `solid` is device memory of the context's
  * device, read by work enqueued on `stream` during this call only; otherwise host memory.  The call returns once the mask has been read;
@@ -875,6 +877,75 @@ int fx_set_particle_draw(fx_ctx* ctx, const fx_particle_draw* draw);
 int fx_get_particle_draw(fx_ctx* ctx, fx_particle_draw* out);
 int fx_draw_particles(fx_ctx* ctx, void* stream, uint8_t frame_index);
 int fx_particle_splats(fx_ctx* ctx, void* stream, uint64_t* out, size_t bytes);
+
+/* The obstacle draw (no reference counterpart): the solid cells of the mask in force -- whichever of fx_set_obstacles and fx_set_obstacle_meshes
+ * put it there, resting or moving (fx_set_obstacle_bodies) -- ray-cast into the render target and into a depth buffer.  Per pixel the view ray walks the
+ * voxel mask to the first solid cell; the face it entered through is shaded with the light of fx_set_light and written, opaque, with its D3D
+ * depth.  With that depth attached (fx_set_scene_depth, FX_DEPTH_DEVICE) the marches end at the solid: smoke in front of it blends over it,
+ * smoke behind it is hidden, fx_draw_particles culls what lies behind it.  No march kernel knows of it.  The frame order becomes: clear,
+ * environment, fx_draw_obstacles, fx_render (with the obstacle depth attached), fx_draw_particles.  Off by default: a context that never
+ * calls the setter launches, computes and counts what it did before.
+ * The rule, fp32, every operation rounded as written, fma only where it says so (tests/obstacle_draw_ref.py restates it in numpy).
+ * N = (X, Y, Z) the grid, S(i) = bit 6 of the code byte of cell i = (i_0, i_1, i_2) = (x, y, z), (W, H) = the viewport.
+ *   ray      (o, d) = what fx_render's direct march casts for the pixel: the pixel's ray and its origin moved onto the volume's box
+ *            (PSRayCast.hlsl:17-26,47-50, ComputeRayOrigin); a pixel that discards is a miss.  e = the entry axis of ComputeRayOrigin, the axis
+ *            whose quotient became U (the lowest on a tie); none when the eye lies inside the box
+ *   start    s_a = fma(o_a, .5, .5);  i_a = min(max((int)floorf(s_a * N_a), 0), N_a - 1);  st_a = +1 / -1 / 0 for d_a > 0 / d_a < 0 / otherwise
+ *            (a -0 or a NaN gives 0);  r_a = 1.0f / d_a.  If S(i): a hit at t = 0, p = o, face = 2e + (d_e > 0) with an entry axis, 6 without
+ *   walk     per axis n_a = i_a + (st_a > 0);  P_a = fma((float)n_a / (float)N_a, 2, -1);  t_a = st_a ? (P_a - o_a) * r_a : FLT_MAX.
+ *            The step axis a* = (t_0 <= t_1 && t_0 <= t_2) ? 0 : (t_1 <= t_2) ? 1 : 2 (the smallest t, ties to the lowest axis, a NaN loses).
+ *            st_a* == 0: a miss (the walk cannot move).  i_a* += st_a*;  off the grid on that axis: a miss;  S(i): a hit with t_hit = t_a*
+ *            (taken before the advance), face = 2 a* + (st_a* > 0), normal = -st_a* e_a*, p_a = fma(d_a, t_hit, o_a).  After X + Y + Z advances
+ *            without a hit: a miss.  Every t is a function of an integer plane index and nothing accumulates, so a walk that skips what it knows
+ *            to be empty reproduces this one bit for bit, and the cap ends it whatever the matrices held
+ *   visible  h_r = fma(1, M[4r+3], fma(p_2, M[4r+2], fma(p_1, M[4r+1], p_0 * M[4r+0]))), M = the forward WorldViewProj rows (the chain of the
+ *            particle draw's project, on p itself);  cz = h_2 / h_3.  Drawn iff h_3 > 0 && 0 <= cz && cz < 1 && (no scene depth ||
+ *            cz <= scene[py][px]), written so that a NaN is not drawn: a hit in front of the near plane is clipped away, as a rasteriser would
+ *   shade    L = the unit vector the shadow rays run along: the local light direction (FX_LIGHT_DIRECTIONAL) or the direction from p to the
+ *            local light point, 0 where the marches cast no ray (FX_LIGHT_POINT).  With st = +1 for an odd face, -1 for an even one and
+ *            a = face / 2:  ndl = face < 6 ? fmaxf(0, (float)(-st) * L_a) : 0;  k_c = albedo[c] * albedo[3];
+ *            src_c = (k_c * fma(ndl, color[3] * color[c], ambient[3] * ambient[c])) * 0.159154937f for c = r, g, b (the light's colour and
+ *            ambient of fx_set_light; the ambient term also while a light probe is set)
+ *   store    a drawn pixel: target = (unorm8(src_r), unorm8(src_g), unorm8(src_b), 255) -- an opaque overwrite, no blend --,
+ *            FX_FIELD_TARGET_FLOAT = (src, 1), depth-out = cz.  Every other pixel: the target keeps its bytes, FX_FIELD_TARGET_FLOAT = 0,
+ *            depth-out = the scene depth, or 1.0 without one.  The hits word (fx_obstacle_hits) of a pixel whose walk hit, drawn or not:
+ *            bit 63 set, bit 62 = drawn, bits 32-34 = face, bits 0-31 = (z * Y + y) * X + x of the cell; a miss is 0
+ * No value reaches an index unclamped or untested, and the only loop is bounded by the cap.
+ * fx_set_obstacle_draw with a struct does all the allocation: the depth-out buffer (W * H floats, filled with 1.0), the brick volume the cast
+ * walks through (one uint64 per 4 x 4 x 4 cells: bit (z & 3) * 16 + (y & 3) * 4 + (x & 3) = S, cells beyond the grid 0) and the render
+ * target where no render has allocated it yet; FX_E_NOMEM if that fails, the previous state staying in force.  NULL = off (the default), which
+ * frees the first two.  fx_get_obstacle_draw: the setting in force; off reports albedo 0.
+ * fx_draw_obstacles only enqueues -- it never allocates, copies to the host or waits, and stays capturable: the cast (fx_obstacle_draw.hip
+ * k_obstacle_cast), and in front of it the pack of the brick volume (k_obstacle_pack) when the mask has changed since the last pack, so that a
+ * mask set between two draws is seen by the second.  It uses the camera of the last fx_update_frame that carried matrices and the light of
+ * fx_set_light.  scene_depth_device is optional: the caller's own scene, float[H][W] on the context's device, D3D convention; a hit behind it
+ * is not drawn.  It must not be the depth-out buffer.  With no mask in force, or one without a solid cell: FX_OK, the target untouched,
+ * depth-out = the scene depth (1.0 without one), FX_FIELD_TARGET_FLOAT all zero.  Timing: booked into fx_timing.resolve_ms; not a render.
+ * fx_obstacle_depth_device: the depth-out buffer, float[H][W] on the device; NULL while the draw is off.  One call attaches it:
+ * fx_set_scene_depth(ctx, stream, depth, W, H, z_near, z_far, FX_DEPTH_DEVICE).  The renders read it in place and fx_draw_obstacles rewrites
+ * it each frame on the same stream.  The pointer is valid until the next fx_set_obstacle_draw or fx_destroy; switching the draw off while it
+ * is attached is the caller's error (detach first: fx_set_scene_depth(ctx, stream, NULL, ...)).
+ * fx_obstacle_hits is the inspection call: the same cast, storing neither target nor depth-out, its hits words and depths copied to the host
+ * pointers hits_out and depth_out (either may be NULL), pixels = W * H each; blocks.
+ * Configuration on the particle draw's terms: per context, kept across fx_update_frame, not checkpointed, not part of fx_field_digest.
+ * FX_E_INVALID, the previous state staying in force: a NULL ctx or out-pointer, a wrong struct_size, unknown flag bits, a non-finite or
+ * negative albedo member, pixels != W * H, a frame_index >= FX_FRAME_COUNT, scene_depth_device = the depth-out buffer, and (all but
+ * fx_get_obstacle_draw and fx_obstacle_depth_device, which report the default there) a 2-D grid, a context without a viewport, a slab rank, a
+ * grid of 2^32 cells or more.  FX_E_STATE: FX_FLAG_RENDER_ONLY contexts, which have no obstacles; fx_draw_obstacles and fx_obstacle_hits while
+ * the draw is off or before an fx_update_frame gave a camera (as fx_render).  FX_E_NOMEM: a buffer cannot be allocated.
+ * Out of scope: solids casting shadows into the smoke (the light marches do not see the mask -- the obvious next step); smoke shadowing the
+ * solids (a light-map fetch at the hit); SH irradiance on solids; per-body or per-mesh colours (the code byte carries no body); smooth normals;
+ * drawing into the cube map; slab, render-only and 2-D contexts; checkpointing. */
+typedef struct fx_obstacle_draw {
+	uint32_t struct_size, flags;   /* sizeof(fx_obstacle_draw) = 24; flags: 0 */
+	float albedo[4];               /* rgb x intensity (w); finite, >= 0 */
+} fx_obstacle_draw;
+int fx_set_obstacle_draw(fx_ctx* ctx, const fx_obstacle_draw* draw);
+int fx_get_obstacle_draw(fx_ctx* ctx, fx_obstacle_draw* out);
+int fx_draw_obstacles(fx_ctx* ctx, void* stream, uint8_t frame_index, const float* scene_depth_device);
+int fx_obstacle_depth_device(fx_ctx* ctx, void** depth);
+int fx_obstacle_hits(fx_ctx* ctx, void* stream, uint8_t frame_index, const float* scene_depth_device,
+	uint64_t* hits_out, float* depth_out, size_t pixels);
 
 /* The advection scheme (no reference counterpart: the reference's CSAdvect is a first-order semi-Lagrangian step, the main source of the blur
  * the confinement fights).  FX_ADVECT_MACCORMACK is the scheme of Selle, Fedkiw, Kim, Liu, Rossignac 2008 (also Crane et al., GPU Gems 3
